@@ -1,6 +1,6 @@
 """Benchmark of the recoup coverage -> profile hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 `--gpus N > 1` without a torch.distributed environment (WORLD_SIZE unset) starts the N ranks
@@ -19,11 +19,27 @@ path (strong scaling: value = all regions x bins / the slowest rank's time).  Th
 reassembly of the R x B matrix (one RCCL all_gather over xGMI) is timed separately
 (`gather`), never inside `value`.
 
-Prints ONE JSON line (rank 0): value = region-bins/s of the whole job, plus
-  roofline      the pileup kernel's algorithmic bytes / its HIP-event-timed duration (rank 0's
-                shard), PMC traffic of the same kernel when profiles/ holds it, and the
-                whole-step fraction
-  cpu_baseline  the CPU oracle (test infrastructure, `oracle/`) on a bounded sample, timed here
+A plain run does only what `value` needs: it builds the workload, warms up, picks the samples in
+flight, times exactly --steps steps and prints ONE JSON line (rank 0): value = region-bins/s of
+the whole job, ms_per_step = the milliseconds one timed step took.  `--dump-outputs DIR` also
+writes what the last timed step computed (below).  `--full` adds everything else, each in runs
+of its own after the timed steps (a plain run prints null in their places):
+  inflight_check  every sample of the timed steps bit for bit against the general pileup kernel
+  kernel_ms       per-stage durations between HIP events
+  roofline        the pileup kernel's algorithmic bytes / its HIP-event-timed duration (rank 0's
+                  shard), PMC traffic of the same kernel when profiles/ holds it, and the
+                  whole-step fraction
+  gather          N > 1: the reassembly of the R x B matrix (also with --verify-gather alone)
+  e2e             host-to-host passes through the C ABI entry points
+  cpu_baseline    the CPU oracle (test infrastructure, `oracle/`) on a bounded sample, timed here,
+                  and parity_sample, the GPU pass against it
+
+`--dump-outputs DIR` (rank 0): the arrays a caller of the timed path receives from its last timed
+step -- the R x B profile matrix and the row validity of sample 0, which the last step always
+runs -- as DIR/profile.npy (float64; the rows listed in DIR/profile_rows.npy, a fixed sample
+drawn from --seed when the matrix is larger than 48 MiB) and DIR/valid.npy (float32, the same
+rows).  The workload is a function of the arguments alone, so two builds run with the same
+arguments can be compared file by file.
 """
 import argparse
 import json
@@ -38,6 +54,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
+TUNE_PASSES = 200  # most passes per candidate when the samples in flight are picked
+DUMP_BYTES = 48 << 20  # --dump-outputs: most bytes of the profile matrix written
 
 
 # plan.info["pileup_kernel"] -> kernel name (as rocprofv3 lists it)
@@ -66,10 +84,16 @@ def parse():
     ap.add_argument("--kernel", default="auto", help="pileup kernel of the timed plans (A/B; default auto)")
     ap.add_argument("--inflight", default="auto", choices=["auto", "1", "2", "3", "4"],
                     help="samples in flight: D DISTINCT samples (independent read sets over the same region "
-                         "table, as profileMatrix loops over a recoup input list) on D HIP streams, step k "
-                         "= one complete pass of sample k %% D; auto (default): the fastest of 1, 2, 3, 4, "
+                         "table, as profileMatrix loops over a recoup input list) on D HIP streams, every step "
+                         "one complete pass of the next sample in turn; auto (default): the fastest of 1, 2, 3, 4, "
                          "timed on every rank (max over ranks) so all ranks run the same D.  The "
                          "one-sample pass time is always reported beside it (single_pass_ms)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (profile.npy, profile_rows.npy, valid.npy) to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what `value` does not need: the bit-for-bit check against the general kernel, "
+                         "per-kernel and roofline timings, the gather (N > 1), the host-to-host e2e passes and "
+                         "the CPU baseline with its parity check")
     ap.add_argument("--traffic", default=None,
                     help="PMC traffic summary (tools/pmc_traffic.py); default profiles/traffic_<config>.json")
     return ap.parse_args()
@@ -88,10 +112,11 @@ WORKLOADS = {
 }
 
 
-def workload(args, dev, sample=0):
+def workload(args, dev, sample=0, counts=True):
     """(data, RowTable, Bins, per-row overlapping read-segment pairs) of the chosen BASELINE
     config.  Every rank generates the SAME data (one seed, Philox on the device); ``sample`` k
-    > 0 is another sample's reads over the same regions."""
+    > 0 is another sample's reads over the same regions.  ``counts`` False: None in place of
+    the overlap counts (two sorts of the reads that only sharding and the roofline need)."""
     import synthetic
     from recoup_amd.engine import Bins, RowTable
     seed = args.seed
@@ -105,6 +130,8 @@ def workload(args, dev, sample=0):
         rows = synthetic.rna_rows(d)
         bins = Bins([("upstream", d["flank_bins"]), ("center", d["region_bins"]), ("downstream", d["flank_bins"])],
                     flank=d["flank"])
+        if not counts:
+            return d, rows, bins, None
         seg = synthetic.n_overlaps_segments(d["reads"], rows.chrom, rows.start, rows.end, device=dev)
         ovl = np.add.reduceat(seg, rows.seg_off[:-1]) if len(seg) else np.zeros(rows.n_rows, np.int64)
         return d, rows, bins, ovl.astype(np.int64)
@@ -117,6 +144,8 @@ def workload(args, dev, sample=0):
     reg = d["regions"]
     rows = RowTable.from_ranges(reg["chrom"], reg["start"], reg["end"], reg["strand"])
     bins = Bins([("whole", d["n_bins"])]) if d["n_bins"] > 0 else Bins([("whole", 0, sum(d["flank"]))])
+    if not counts:
+        return d, rows, bins, None
     ovl = synthetic.n_overlaps(d["reads"], reg, d["width"], device=dev).astype(np.int64)
     return d, rows, bins, ovl
 
@@ -263,6 +292,8 @@ def devices_used(world, n_visible, share):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise Refused(f"--steps {args.steps}: at least one timed step")
     n_visible = torch.cuda.device_count()
     share = os.environ.get("RCP_SHARE_GPU") == "1"
     world, cmd = launch_plan(args, os.environ, n_visible, sys.argv[1:])
@@ -303,13 +334,18 @@ def main():
     from recoup_amd.engine import Plan, ReadSet
 
     t0 = time.time()
-    data, rows_all, bins, ovl_all = workload(args, dev)
-    R_total = rows_all.n_rows
-    n_reads_total = int(data["reads"][1].numel())
     s_rank, s_world = rank, world
     if args.sim_shard:
         s_rank, s_world = (int(x) for x in args.sim_shard.split("/"))
-    lo, hi, cuts = shard_of(rows_all, ovl_all, s_world, s_rank)
+    # the per-row overlap counts balance the shards and size the roofline: one whole table on a
+    # plain run needs neither
+    data, rows_all, bins, ovl_all = workload(args, dev, counts=s_world > 1 or args.full)
+    R_total = rows_all.n_rows
+    n_reads_total = int(data["reads"][1].numel())
+    if ovl_all is None:
+        lo, hi, cuts = 0, R_total, np.array([0, R_total])
+    else:
+        lo, hi, cuts = shard_of(rows_all, ovl_all, s_world, s_rank)
     rows = subset_rows(rows_all, lo, hi) if s_world > 1 else rows_all
     reads = reads_for_rows(data["reads"], rows, len(data["seqlen"])) if s_world > 1 else data["reads"]
     if world > 1 and not args.verify_gather:
@@ -349,7 +385,7 @@ def main():
     dmax = 4 if args.inflight == "auto" else int(args.inflight)
     if dmax > 1:
         for k in range(1, dmax):
-            dk = workload(args, dev, sample=k)[0]
+            dk = workload(args, dev, sample=k, counts=False)[0]
             rk = reads_for_rows(dk["reads"], rows, len(dk["seqlen"])) if s_world > 1 else dk["reads"]
             rsets.append(ReadSet(*rk, dk["seqlen"], device=local))
             del dk, rk
@@ -358,12 +394,12 @@ def main():
         outs = [p.empty_output() for p in plans]
         streams = [torch.cuda.Stream(device=dev) for _ in range(dmax)]
 
-    def passes(D, n):
+    def passes(D, n, first=0):
         for k in range(n):
             if D == 1:
                 plan.execute(out, valid, stream=streams[0])
                 continue
-            i = k % D
+            i = (first + k) % D
             plans[i].execute(outs[i], valids[i], stream=streams[i])
 
     # ---- warmup + correctness gate
@@ -372,13 +408,16 @@ def main():
         passes(len(plans), max(args.warmup, len(plans)))
     for p in plans + [plan]:
         p.status()
+    # (as many passes per D as timed steps, between 10 and TUNE_PASSES: a run of many steps does not
+    # spend several times its timed region here)
     tune = {}
+    n_tune = min(max(args.steps, 10), TUNE_PASSES)
     for d in ([1] + ([2, 3, 4] if args.inflight == "auto" else [])):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        passes(d, max(args.steps, 10))
+        passes(d, n_tune)
         torch.cuda.synchronize()
-        tune[d] = (time.perf_counter() - t) / max(args.steps, 10) * 1e3
+        tune[d] = (time.perf_counter() - t) / n_tune * 1e3
     if dist and len(tune) > 1:  # one D for every rank: the per-D times, max over ranks
         tt = torch.tensor([tune[k] for k in sorted(tune)], dtype=torch.float64,
                           device=dev if backend == "nccl" else "cpu")
@@ -386,12 +425,14 @@ def main():
         tune = {k: float(v) for k, v in zip(sorted(tune), tt.tolist())}
     D = min(tune, key=tune.get) if args.inflight == "auto" else len(plans)
 
-    # ---- timed region: exactly K steps between barrier + synchronize
+    # ---- timed region: exactly K steps between barrier + synchronize.  The round over the D
+    # samples starts where it ends on sample 0 at the last step, whatever D was picked: that
+    # step's output is the one --dump-outputs writes
     if dist:
         tdist.barrier()
     torch.cuda.synchronize()
     ts = time.perf_counter()
-    passes(D, args.steps)
+    passes(D, args.steps, first=-(args.steps - 1) % D)
     torch.cuda.synchronize()
     if dist:
         tdist.barrier()
@@ -402,57 +443,33 @@ def main():
         elapsed = float(t.item())
     for p in plans + [plan]:
         p.status()
-    # every sample the timed passes computed, checked bit for bit against an independent plan of
-    # its readset on the general pileup kernel (sample 0 is also checked against the oracle below)
-    inflight_check = []
-    for i in range(D):
-        ref_plan = Plan(rsets[i], rows, bins, kernel="general", out_ld="padded")
-        ref_out = ref_plan.execute()
-        ref_plan.status()
-        got = (outs[i] if D > 1 else out)[:, :R]
-        inflight_check.append(bool(torch.equal(got.view(torch.int64), ref_out[:, :R].view(torch.int64))))
-        del ref_plan, ref_out
+    units = R_total * B  # region-bins per step of the whole job
+    if args.sim_shard:
+        units = R * B  # a rehearsal of one shard: its own region-bins
+    value = units * args.steps / elapsed
+    step_ms = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:  # the last timed step ran sample 0
+        dump_outputs(args.dump_outputs, outs[0] if D > 1 else out, valids[0] if D > 1 else valid, R, B, args.seed)
 
-    # ---- per-kernel durations with HIP events on the launch stream.  A short sleep kernel first
-    # keeps the stream busy while the host enqueues the three stages, so a stage's interval is its
-    # kernels' time, not the host's launch latency (a folded plan's locate stage is empty: its
-    # pileup would otherwise start only when the host gets to it)
-    stream = torch.cuda.current_stream()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    kt = np.zeros(3)
-    for _ in range(args.steps):
-        gpu_sleep(200e-6)
-        ev[0].record(stream)
-        plan.execute_stages(1, out, valid)
-        ev[1].record(stream)
-        plan.execute_stages(2, out)
-        ev[2].record(stream)
-        plan.execute_stages(4, out)
-        ev[3].record(stream)
-        torch.cuda.synchronize()
-        kt += [ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3])]
-    kt /= args.steps  # ms per launch
-    # the pileup kernel alone: 8 launches back to back between two events (each stage interval
-    # above also holds ~9 us of event overhead -- the empty stages' own intervals -- which is a
-    # third of a C2 launch); every pileup kernel resets its own work counters, so the stage can
-    # run again on the same locate outputs
-    k_pile = 0.0
-    for _ in range(max(1, args.steps // 4)):
-        gpu_sleep(400e-6)
-        ev[0].record(stream)
-        for _ in range(8):
-            plan.execute_stages(2, out)
-        ev[1].record(stream)
-        torch.cuda.synchronize()
-        k_pile += ev[0].elapsed_time(ev[1]) / 8
-    k_pile /= max(1, args.steps // 4)
-    plan.status()
-    heavy = plan.heavy_rows()
+    # ---- everything below is measured or checked in runs of its own, beside `value`: --full
+    inflight_check = kt = heavy = roofline = ovl = gather = e2e = cpu = parity = None
+    if args.full:
+        # every sample the timed passes computed, checked bit for bit against an independent plan of
+        # its readset on the general pileup kernel (sample 0 is also checked against the oracle below)
+        inflight_check = []
+        for i in range(D):
+            ref_plan = Plan(rsets[i], rows, bins, kernel="general", out_ld="padded")
+            ref_out = ref_plan.execute()
+            ref_plan.status()
+            got = (outs[i] if D > 1 else out)[:, :R]
+            inflight_check.append(bool(torch.equal(got.view(torch.int64), ref_out[:, :R].view(torch.int64))))
+            del ref_plan, ref_out
+        inflight_check = {"samples": D, "equal_to_general_kernel": inflight_check}
+        kt, k_pile, heavy = kernel_times(plan, out, valid, args.steps)
 
     # ---- reassembly of the R x B matrix (not in `value`): one all_gather of each rank's
     # column-major block, padded to the largest shard, then placement into region order
-    gather = None
-    if dist:
+    if dist and (args.full or args.verify_gather):
         gather, full = gather_matrix(tdist, backend, out, R, B, cuts, dev, R_total)
         if args.verify_gather and rank == 0:
             rs_all = ReadSet(*data["reads"], data["seqlen"], device=local)
@@ -463,31 +480,40 @@ def main():
             del rs_all, ref
         del full
 
-    units = R_total * B  # region-bins per step of the whole job
-    if args.sim_shard:
-        units = R * B  # a rehearsal of one shard: its own region-bins
-    value = units * args.steps / elapsed
-    ovl = int(np.asarray(ovl_all)[lo:hi].sum())
-    # 8 B per overlapping (read, segment) + 16 B per region + 8 B per further segment
-    # of a multi-range row + the f64 output written once (this rank's shard)
-    n_seg = len(rows.start)
-    bytes_pileup = 8 * ovl + 16 * R + 8 * (n_seg - R) + 8 * R * B
-    if args.config == "c3":  # + 4 R (B + 1): the per-row bin tables of non-uniform (R-RNG) layouts
-        bytes_pileup += 4 * R * (B + 1)
-    achieved = bytes_pileup / (k_pile * 1e-3) / 1e9
-    # the same with the bytes the kernel actually streams per read: 4 for reads of one width whose
-    # starts alone the kernel loads (C2, C5; C4's binned lean kernel loads the pairs)
-    rb = int(plan.info.get("read_bytes", 8))
-    bytes_streamed = bytes_pileup - (8 - rb) * ovl
-    kernel = PILEUP_KERNELS[plan.info["pileup_kernel"]]
-    traffic = load_traffic(args.traffic or os.path.join(ROOT, "profiles", f"traffic_{args.config}.json"), args,
-                           kernel, R, n_reads, world)
-    step_ms = elapsed / args.steps * 1e3
+    if args.full:
+        ovl = int(np.asarray(ovl_all)[lo:hi].sum())
+        # 8 B per overlapping (read, segment) + 16 B per region + 8 B per further segment
+        # of a multi-range row + the f64 output written once (this rank's shard)
+        n_seg = len(rows.start)
+        bytes_pileup = 8 * ovl + 16 * R + 8 * (n_seg - R) + 8 * R * B
+        if args.config == "c3":  # + 4 R (B + 1): the per-row bin tables of non-uniform (R-RNG) layouts
+            bytes_pileup += 4 * R * (B + 1)
+        achieved = bytes_pileup / (k_pile * 1e-3) / 1e9
+        # the same with the bytes the kernel actually streams per read: 4 for reads of one width whose
+        # starts alone the kernel loads (C2, C5; C4's binned lean kernel loads the pairs)
+        rb = int(plan.info.get("read_bytes", 8))
+        bytes_streamed = bytes_pileup - (8 - rb) * ovl
+        kernel = PILEUP_KERNELS[plan.info["pileup_kernel"]]
+        traffic = load_traffic(args.traffic or os.path.join(ROOT, "profiles", f"traffic_{args.config}.json"), args,
+                               kernel, R, n_reads, world)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                    "kernel": kernel,
+                    "algorithmic_bytes_per_launch": bytes_pileup,
+                    "read_bytes": rb,
+                    "frac_streamed_bytes": bytes_streamed / (k_pile * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                    "streamed_bytes_note": "frac with the bytes per read the kernel loads (read_bytes) instead of "
+                                           "SURVEY 8(d)'s 8: the start-only stream of reads of one width",
+                    "kernel_ms": k_pile,
+                    "kernel_ms_note": "the pileup stage's kernel(s) per launch, 8 launches back to back between "
+                                      "two HIP events on the launch stream (kernel_ms below: one stage per "
+                                      "event pair, each interval with ~9 us of event overhead)",
+                    "step_frac": bytes_pileup / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS if world == 1 else None}
+        kt = {"locate": kt[0], "pileup": kt[1], "interp": kt[2]}
 
     # ---- end to end once (not `value`): what a host caller (the R shim's rcp_profile) pays --
     # host read arrays -> H2D + device sort (readset), plan, one pass, D2H of the matrix
-    e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         e2e = end_to_end(reads, data["seqlen"], rows, bins, local, R * B)
         if dist:
             t = torch.tensor([e2e["ms"]], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -497,9 +523,7 @@ def main():
             e2e["note"] += "; per rank on its shard, max over ranks"
 
     # ---- CPU baseline (rank 0, N = 1): the oracle on a bounded sample of the same workload
-    cpu = None
-    parity = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.sim_shard:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.sim_shard:
         cpu, parity = cpu_baseline(args, data, rows, bins, plan, B)
 
     if rank == 0:
@@ -532,32 +556,77 @@ def main():
                                  "ms per pass by D: " + json.dumps({str(k): round(v, 4) for k, v in tune.items()}),
                 "single_pass_ms": tune[1],
             },
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                         "kernel": kernel,
-                         "algorithmic_bytes_per_launch": bytes_pileup,
-                         "read_bytes": rb,
-                         "frac_streamed_bytes": bytes_streamed / (k_pile * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                         "streamed_bytes_note": "frac with the bytes per read the kernel loads (read_bytes) instead of "
-                                                "SURVEY 8(d)'s 8: the start-only stream of reads of one width",
-                         "kernel_ms": k_pile,
-                         "kernel_ms_note": "the pileup stage's kernel(s) per launch, 8 launches back to back between "
-                                           "two HIP events on the launch stream (kernel_ms below: one stage per "
-                                           "event pair, each interval with ~9 us of event overhead)",
-                         "step_frac": bytes_pileup / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS if world == 1 else None},
+            "full": args.full,
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "e2e": e2e,
             "gather": gather,
-            "kernel_ms": {"locate": kt[0], "pileup": kt[1], "interp": kt[2]},
+            "kernel_ms": kt,
             "heavy_rows": heavy,
             "n_overlaps": ovl,
             "plan_ms": plan_s * 1e3,
             "parity_sample": parity,
-            "inflight_check": {"samples": D, "equal_to_general_kernel": inflight_check},
+            "inflight_check": inflight_check,
+            "outputs": args.dump_outputs,
         }
         print(json.dumps(res), flush=True)
     if dist:
         tdist.destroy_process_group()
+
+
+def kernel_times(plan, out, valid, steps):
+    """Per-kernel durations with HIP events on the launch stream: (ms per launch of the locate,
+    pileup and interpolation stages, ms of the pileup stage alone, heavy rows of the last pass).
+    A short sleep kernel first keeps the stream busy while the host enqueues the three stages, so
+    a stage's interval is its kernels' time, not the host's launch latency (a folded plan's locate
+    stage is empty: its pileup would otherwise start only when the host gets to it)."""
+    stream = torch.cuda.current_stream()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    kt = np.zeros(3)
+    for _ in range(steps):
+        gpu_sleep(200e-6)
+        ev[0].record(stream)
+        plan.execute_stages(1, out, valid)
+        ev[1].record(stream)
+        plan.execute_stages(2, out)
+        ev[2].record(stream)
+        plan.execute_stages(4, out)
+        ev[3].record(stream)
+        torch.cuda.synchronize()
+        kt += [ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2]), ev[2].elapsed_time(ev[3])]
+    kt /= steps  # ms per launch
+    # the pileup kernel alone: 8 launches back to back between two events (each stage interval
+    # above also holds ~9 us of event overhead -- the empty stages' own intervals -- which is a
+    # third of a C2 launch); every pileup kernel resets its own work counters, so the stage can
+    # run again on the same locate outputs
+    k_pile = 0.0
+    for _ in range(max(1, steps // 4)):
+        gpu_sleep(400e-6)
+        ev[0].record(stream)
+        for _ in range(8):
+            plan.execute_stages(2, out)
+        ev[1].record(stream)
+        torch.cuda.synchronize()
+        k_pile += ev[0].elapsed_time(ev[1]) / 8
+    k_pile /= max(1, steps // 4)
+    plan.status()
+    return kt, k_pile, plan.heavy_rows()
+
+
+def dump_outputs(path, out, valid, R, B, seed):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step -- rows of
+    the R x B profile matrix (``out`` is its column-major device buffer, the matrix out[:, :R])
+    and the row validity.  All rows when they fit DUMP_BYTES, else a sorted sample of them drawn
+    from ``seed``; profile_rows.npy lists the rows written, valid.npy covers the same rows."""
+    os.makedirs(path, exist_ok=True)
+    n = min(R, max(1, DUMP_BYTES // (8 * max(B, 1))))
+    idx = np.arange(R) if n == R else np.sort(np.random.default_rng(seed).choice(R, n, replace=False))
+    ix = torch.as_tensor(idx, dtype=torch.int64, device=out.device)
+    prof = out[:, :R].index_select(1, ix).t().contiguous().cpu().numpy()
+    np.save(os.path.join(path, "profile.npy"), prof.astype(np.float64, copy=False))
+    np.save(os.path.join(path, "profile_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "valid.npy"), valid[:R].index_select(0, ix).cpu().numpy().astype(np.float32))
+    log(f"bench.py: wrote rows {n} of {R} x {B} columns to {path}")
 
 
 def gather_matrix(tdist, backend, out, R, B, cuts, dev, R_total, reps=3):

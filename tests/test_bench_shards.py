@@ -79,6 +79,58 @@ def test_shards_balance_by_overlaps():
         assert max(loads) <= w.sum() / world + w.max() + 1e-9
 
 
+def _device_output(R, B, ld, seed=11):
+    """A column-major output buffer as a plan fills it: (B, ld) float64, the matrix in [:, :R]."""
+    rng = np.random.default_rng(seed)
+    out = torch.full((B, ld), -7.0, dtype=torch.float64)
+    out[:, :R] = torch.as_tensor(rng.random((B, R)))
+    valid = torch.as_tensor((rng.random(max(R, 1)) < 0.8).astype(np.uint8))
+    return out, valid
+
+
+def test_dump_outputs_writes_the_whole_small_matrix(tmp_path):
+    R, B = 37, 5
+    out, valid = _device_output(R, B, ld=48)
+    bench.dump_outputs(str(tmp_path / "d"), out, valid, R, B, seed=3)
+    prof = np.load(tmp_path / "d" / "profile.npy")
+    rows = np.load(tmp_path / "d" / "profile_rows.npy")
+    v = np.load(tmp_path / "d" / "valid.npy")
+    assert prof.dtype == np.float64 and rows.dtype == np.float64 and v.dtype == np.float32
+    np.testing.assert_array_equal(rows, np.arange(R))
+    np.testing.assert_array_equal(prof, out[:, :R].numpy().T)  # the R x B matrix, padding left out
+    np.testing.assert_array_equal(v, valid[:R].numpy())
+
+
+def test_dump_outputs_samples_a_large_matrix_the_same_way_every_time(tmp_path, monkeypatch):
+    R, B = 1000, 16
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * B * 100)  # room for 100 rows
+    out, valid = _device_output(R, B, ld=1008)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, valid, R, B, seed=20261015)
+    rows = np.load(tmp_path / "a" / "profile_rows.npy").astype(np.int64)
+    assert len(rows) == 100 and len(np.unique(rows)) == 100 and np.all(np.diff(rows) > 0)
+    assert rows.min() >= 0 and rows.max() < R
+    prof = np.load(tmp_path / "a" / "profile.npy")
+    assert prof.nbytes <= 8 * B * 100
+    np.testing.assert_array_equal(prof, out[:, :R].numpy().T[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "valid.npy"), valid.numpy()[rows])
+    for f in ("profile.npy", "profile_rows.npy", "valid.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    # another seed, another sample
+    bench.dump_outputs(str(tmp_path / "c"), out, valid, R, B, seed=1)
+    assert not np.array_equal(np.load(tmp_path / "c" / "profile_rows.npy"), rows)
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "x"
+    assert bench.DUMP_BYTES <= 48 << 20  # with the row list and the validity: under 64 MB in all
+
+
 class _Args:
     def __init__(self, gpus):
         self.gpus = gpus

@@ -31,7 +31,7 @@ if has share2; then
   python3 -c "import json; d=json.loads([l for l in open('$OUT/share2_c4.json') if l.startswith('{')][-1]); print('share2', d['n_gpus'], d['devices_used'], d['value'], d['ms_per_step'], d['config']['shards'], d['gather'])"
 fi
 if has c4; then
-  timeout -k 10 600 python3 bench.py > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" || { tail -30 "$OUT/c4_bench.err"; exit 1; }
+  timeout -k 10 600 python3 bench.py --full > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" || { tail -30 "$OUT/c4_bench.err"; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/c4_bench.json')); e=d['e2e']
 print('C4', d['value'], d['ms_per_step'], d['config']['single_pass_ms'], d['roofline']['frac'], d['roofline']['kernel_ms'])
@@ -39,21 +39,21 @@ print('e2e', round(e['ms'],2), e['equal_two_calls'], 'two calls', round(e['two_c
 fi
 if has shards; then
   for c in c4 c5; do
-    timeout -k 10 300 python3 bench.py --config $c --sim-shard 0/8 --inflight 1 --no-e2e --no-cpu > "$OUT/${c}_shard.json" 2> "$OUT/${c}_shard.err" || { tail -30 "$OUT/${c}_shard.err"; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --config $c --sim-shard 0/8 --inflight 1 --no-e2e --no-cpu > "$OUT/${c}_shard.json" 2> "$OUT/${c}_shard.err" || { tail -30 "$OUT/${c}_shard.err"; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/${c}_shard.json')); print('$c shard', d['ms_per_step'], d['config'].get('single_pass_ms'), d.get('kernel_ms'), d['roofline']['kernel'])"
   done
 fi
 if has prof; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-      python3 bench.py --no-cpu --no-e2e --inflight 1 > "$OUT/c4_bench_under_rocprof.json" 2> "$OUT/prof.err" || { tail -30 "$OUT/prof.err"; exit 1; }
+      python3 bench.py --full --no-cpu --no-e2e --inflight 1 > "$OUT/c4_bench_under_rocprof.json" 2> "$OUT/prof.err" || { tail -30 "$OUT/prof.err"; exit 1; }
   find "$OUT/prof" -name "*kernel_stats.csv" | head -3
 fi
 if has configs; then
   for c in ${CONFIGS:-c2 c3 c5}; do
-    timeout -k 10 300 python3 bench.py --config $c --no-e2e > "$OUT/${c}_bench.json" 2> "$OUT/${c}_bench.err" || { tail -30 "$OUT/${c}_bench.err"; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --config $c --no-e2e > "$OUT/${c}_bench.json" 2> "$OUT/${c}_bench.err" || { tail -30 "$OUT/${c}_bench.err"; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/${c}_bench.json')); print('$c', d['value'], d['ms_per_step'], d['config'].get('single_pass_ms'), d['roofline']['kernel'], d['roofline']['kernel_ms'], d['roofline']['frac'])"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o bench -- \
-        python3 bench.py --config $c --no-cpu --no-e2e --inflight 1 > "$OUT/${c}_under_rocprof.json" 2> "$OUT/prof_$c.err" || { tail -30 "$OUT/prof_$c.err"; exit 1; }
+        python3 bench.py --full --config $c --no-cpu --no-e2e --inflight 1 > "$OUT/${c}_under_rocprof.json" 2> "$OUT/prof_$c.err" || { tail -30 "$OUT/prof_$c.err"; exit 1; }
   done
 fi
 exit 0
