@@ -1,6 +1,6 @@
-// rcp_device.h -- device-side plan layout shared by rcp_kernels.hip and rcp_host.cpp.
+// rcp_device.h -- device-side plan layout shared by rcp_kernels.hip and the host sources.
 //
-// All tables are built on the host (rcp_host.cpp) and uploaded once per plan; the
+// All tables are built on the host (rcp_plan.cpp) and uploaded once per plan; the
 // kernels only read them.  Names follow the reference's domain: reads, streams
 // (a (chromosome, strand) run of start-sorted reads), rows (one mask element, or the
 // c(left, exons, right) of coverageRnaRef), segments (the ranges of a row, in output
@@ -71,6 +71,17 @@ struct RcpPart {
     int32_t chunk_bins;  // bins per workgroup chunk
     int32_t n_chunks;    // ceil(n_bins / chunk_bins)
     int32_t lay_base;    // offset of this part's dif -> layout index table (n_bins entries)
+};
+
+// The pileup kernel of a plan (RcpPlanDev::lean, chosen by rcp_plan.cpp plan_shape).  The values
+// are rcp_plan_info.pileup_kernel of the C ABI: fixed.
+enum {
+    RCP_PILEUP_GENERAL = 0,   // rcp_pileup_kernel: any plan
+    RCP_PILEUP_LEAN = 1,      // rcp_pileup_lean_kernel: every row one plain range, uniform power-of-two
+                              //    bins of one wave chunk
+    RCP_PILEUP_LEAN_GEN = 2,  // ... its general-bins mode: any uniform width, R-RNG layouts
+    RCP_PILEUP_ROWS = 3,      // rcp_pileup_rows_kernel: whole rows per wave
+    RCP_PILEUP_BINS = 4       // rcp_pileup_bins_kernel: bin differences, a row per wave pass
 };
 
 struct RcpPlanDev {
@@ -156,8 +167,7 @@ struct RcpPlanDev {
     int32_t n_cus;              // compute units of the plan's device (persistent grid sizing)
     int32_t rounds;             // general pileup kernel: rounds of kTile rows per workgroup (1..4;
                                 //    fewer for small row tables, so more workgroups fill the chip)
-    int32_t lean;               // 1: every row is one plain range with uniform power-of-two bins
-                                //    of one wave chunk -> rcp_pileup_lean_kernel
+    int32_t lean;               // RCP_PILEUP_*: the pileup kernel
     int32_t lean_rounds;        // lean kernel: rounds of 16 rows per work item (2; else kRounds)
     int32_t fold;               // 1: the pileup kernel searches its rows' read ranges itself and applies
                                 //    the NULL rules (no locate / heavy launches; bin-difference plans)
@@ -172,7 +182,7 @@ struct RcpPlanDev {
     int32_t grid_fill;          // eighths of the per-CU workgroup slots persistent pileup grids take
     int32_t lpt_cap;            // items per class list (>= the plan's item count)
     int32_t* item_order;        // [RCP_LPT_CLASSES][lpt_cap]
-    // row-wave kernel (lean == 3): the bin numerators of its rows are staged (uint32, whole
+    // row-wave kernel (RCP_PILEUP_ROWS): the bin numerators of its rows are staged (uint32, whole
     // rows) and the last wave to finish a 16-row tile divides them and writes the tile's rows of
     // every column into the R column-major output as whole 128-B lines (a row-wave store
     // straight into the column-major matrix is 8 bytes per 128-B line).  The stage is

@@ -1,10 +1,11 @@
 // rcp_host.cpp -- host side of librecoup_amd.so: the C ABI of include/recoup_amd.h.
 //
-// Owns device memory (RAII), builds per-plan tables from the reference's semantics and
-// launches the gfx950 kernels in rcp_kernels.hip.  Host work is table construction only
-// (segment orientation, R-RNG bin layouts, chunking); every per-read / per-base operation
-// runs on the GPU.  There is no CPU fallback: without a device every entry point fails with
-// RCP_ENODEVICE.
+// Owns device memory (RAII: the caching allocator), builds readsets, and runs what is made of
+// plans: the one-call profiles, calcCoverage and the Rle paths.  Plans themselves -- the tables
+// built from the reference's semantics (segment orientation, R-RNG bin layouts, chunking), the
+// choice of the pileup kernel and the plan entry points of the C ABI -- live in rcp_plan.cpp.
+// Host work is table construction only; every per-read / per-base operation runs on the GPU.
+// There is no CPU fallback: without a device every entry point fails with RCP_ENODEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,29 +33,6 @@
 #include "rcp_rle.h"
 #include "rcp_rng.h"
 #include "rcp_stage.h"
-
-// auto split off: on one GPU's 1/8, 1/4, 1/2 shard of C4, 4 and 8 column chunks instead of 2
-// were slower (1/8: pileup 0.109 -> 0.143 / 0.203 ms; profiles/r02c/lean_chunk_split_ab.log) --
-// an item's time is set by its 64 rows' read round trips, not by its width
-constexpr int kLeanItemsPerWg = 0;  // work items per persistent workgroup, at least
-// Per-base plans (C5's TSS windows: reads piled in the window's middle, so the middle column
-// chunks are several times the outer ones' work) on few row tiles -- one GPU's shard -- take at
-// least this many work items per workgroup: narrower chunks let the per-XCD claims balance the
-// heavy middle items against the light outer ones (with ~1.5 items per workgroup the pass lasts
-// as long as the slowest workgroup's heavy items)
-constexpr int kLeanItemsPerWgBase = 4;
-constexpr int kLeanMinChunkBins = 64;                   // no column chunks narrower than this
-constexpr int32_t kFoldConcurrentMaxRows = 8192;        // per-base lean fold of plans in flight, rows at most
-// AUTO keeps binned plans of fewer rows on the general kernel: a lean item is 64 rows, the
-// general kernel's workgroup 32, and with about one item per workgroup the item's read round
-// trips set the pass.  C4 shards (1000 bins of 2 bp), ms per pass lean / general: 25 k rows
-// 0.141 / 0.133, 33 k 0.160 / 0.154, 40 k 0.187 / 0.197, 50 k 0.217 / 0.232; per-base C5
-// shards stay lean (12.5 k rows: 0.317 / 0.435).  profiles/r03/pipeline/small_shard_kernels.log
-constexpr int kLeanMinRowsBinned = 36000;
-// Per-base lean plans (baseCoverageMatrix: every part one column per position) take work items
-// of two 16-row rounds instead of four: ms per pass four / two rounds, C5 0.752 / 0.673, its
-// 1/8 shard 0.272 / 0.253, 1/4 0.319 / 0.290; binned C4 is slower with them (0.553 / 0.563
-// pileup; 1/8 shard 0.107 / 0.115).  profiles/r03/pipeline/lean_rounds_ab.log
 
 
 namespace rcpi {
@@ -233,54 +211,16 @@ using namespace rcpi;
 
 namespace {
 
-constexpr int kChunkMax = 16384;       // positions of an interpolated slice (block LDS array)
-constexpr int kWaveMax = 2047;         // positions per wave sub-chunk (64 x 32 slots incl. the end sentinel)
-constexpr int kStageMaxBins = 512;  // bins per chunk (LDS stage = bins x 17 words)
-constexpr size_t kLdsBudget = 80 * 1024;  // pileup LDS per workgroup (80 KB: two per CU)
-constexpr int kHeavyThreshold = 4096;  // candidate reads per column chunk above which a row is split across workgroups
-                                        // (8192 before the lean kernel dealt rows dynamically; C4 0.647 -> 0.633 ms)
 constexpr int kDirReads = 8;  // mean reads per directory bucket (the locate kernel's search depth)
-constexpr int kHeavySlice = 4096;  // candidate reads per heavy work item
-constexpr int kHeavyMaxLen = 16383;    // longer rows never take the heavy path
-constexpr int kHeavyGrid = 4096;
-// general-kernel plans of at most this many rows search their rows' read ranges in the pileup
-// kernel (P.fold): one GPU's share of a region table, where the locate launch and its record round
-// trip are a third of the pass
-constexpr int kFoldMaxRows = 65536;
-// ... and pile a fused-bins chunk of a row with more candidate reads than this with the whole
-// workgroup (8 waves, 16 reads per lane in flight) instead of one wave
-constexpr int kCoopMin = 8192;
-constexpr int kGeneralMaxChunks = 8;  // column chunks a wide binned part is cut into (general kernel)
-
-// A wave's difference array: 64 lanes x per positions (per a power of two >= 4), each lane's
-// chunk padded by 4 words (rcp_kernels.hip scan_wave).  Returns the LDS words and the
-// position capacity for a chunk of `positions`.
-void wave_geometry(int32_t positions, int32_t* words, int32_t* capacity) {
-    int32_t need = (positions + 1 + 63) / 64;
-    int32_t per = 4;
-    while (per < need) per <<= 1;
-    *words = 64 * (per + 4);
-    *capacity = 64 * per - 1;
-}
 
 }  // namespace
+
 
 
 // =====================================================================================
 // readset
 // =====================================================================================
 // phase timing of readset builds and plan creation: stderr lines under RCP_TRACE (rcp_stage.h)
-struct PlanTimer {
-    bool on = rcp::trace_on();
-    double t = on ? rcp::trace_ms() : 0.0;
-    void mark(const char* what) {
-        if (!on) return;
-        const double n = rcp::trace_ms();
-        fprintf(stderr, "[plan] %-14s %8.3f ms\n", what, n - t);
-        t = n;
-    }
-};
-#define PLAN_MARK(what) ptimer.mark(what)
 #define LAYOUT_MARK(what) ((void)(ltimer.on && hipStreamSynchronize(s) == hipSuccess), ltimer.mark(what))
 
 int rcp_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
@@ -458,7 +398,7 @@ int build_layout(const rcp_readset* rs, const rcp_reads_desc* d, const int32_t* 
 
 }  // namespace
 
-namespace {
+namespace rcpi {
 
 // The stranded layout of a readset whose reads were uploaded from the host, built once at its
 // first use from the kept device copies (which are then released).
@@ -489,7 +429,7 @@ int ensure_stranded(const rcp_readset* crs) {
     return RCP_OK;
 }
 
-}  // namespace
+}  // namespace rcpi
 
 namespace rcpi {
 
@@ -792,143 +732,7 @@ extern "C" int rcp_readset_info(const rcp_readset* rs, int64_t* n_reads, int64_t
     RCP_CATCH
 }
 
-// =====================================================================================
-// plan
-// =====================================================================================
-
 namespace {
-
-// A new execution: alternate the status sets (RcpPlanDev::status / status_prev); the locate
-// kernel clears the previous execution's heavy slots and zeroes its set.
-// after an execution's launches on s: the plan's arrays stay allocated until this point (rcp_plan)
-int end_exec(rcp_plan* plan, hipStream_t s) {
-    if (plan->n_streams == 0) {
-        plan->last = s;
-        plan->n_streams = 1;
-    } else if (plan->last != s) {
-        plan->n_streams = 2;
-    }
-    if (!plan->ev_done) HIP_TRY(hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(plan->ev_done, s));
-    return RCP_OK;
-}
-
-void begin_exec(rcp_plan* plan) {
-    plan->epoch ^= 1;
-    plan->dev.status = plan->status_sets + RCP_STATUS_WORDS * plan->epoch;
-    plan->dev.status_prev = plan->status_sets + RCP_STATUS_WORDS * (plan->epoch ^ 1);
-}
-
-struct Builder {
-    // host copies of the device tables
-    std::vector<int32_t> row_chrom, row_seg, row_len;
-    std::vector<uint8_t> row_static;
-    std::vector<RcpSeg> segs;
-    std::vector<int32_t> lay_index, lay_cnt;
-    std::vector<std::pair<int32_t, int32_t>> lay_regions;  // (offset in lay_cnt, n bins)
-    std::vector<int32_t> interp_row, interp_part, interp_mode, interp_pos, nb_pos;
-};
-
-uint8_t stream_mask(int ignore_strand, int8_t q) {
-    // findOverlaps strand compatibility: '*' matches everything (Appendix A, Q2)
-    if (ignore_strand) return 0x1;  // the merged layout: every strand in stream 0
-    if (q == RCP_STRAND_ANY) return 0x7;
-    return (uint8_t)((1u << q) | (1u << RCP_STRAND_ANY));
-}
-
-int build_rows(const rcp_readset* rs, const rcp_rows_desc* rows, Builder* B) {
-    const int R = rows->n_rows;
-    B->row_chrom.assign(R, -1);
-    B->row_seg.assign(R + 1, 0);
-    B->row_len.assign(R, 0);
-    B->row_static.assign(R, 0);
-    for (int r = 0; r < R; ++r) {
-        const int64_t j0 = rows->seg_off[r], j1 = rows->seg_off[r + 1];
-        if (j1 < j0) return fail(RCP_EINVAL, "seg_off not monotone at row %d", r);
-        B->row_seg[r] = (int32_t)B->segs.size();
-        if (j1 == j0) {
-            B->row_static[r] = 1;
-            continue;
-        }
-        const int32_t chrom = rows->seg_chrom[j0];
-        B->row_chrom[r] = chrom;
-        if (chrom < 0 || chrom >= rs->n_chrom) B->row_static[r] = 1;
-        int32_t off = 0;
-        // groups appear as contiguous runs of seg_group
-        int64_t g0 = j0;
-        int prev_group = -1;
-        while (g0 < j1) {
-            const int grp = rows->seg_group ? rows->seg_group[g0] : 0;
-            if (grp < 0 || grp > 3) return fail(RCP_EINVAL, "seg_group %d outside 0..3 (row %d)", grp, r);
-            if (grp <= prev_group) return fail(RCP_EINVAL, "groups of row %d not contiguous/increasing", r);
-            prev_group = grp;
-            int64_t g1 = g0;
-            while (g1 < j1 && (rows->seg_group ? rows->seg_group[g1] : 0) == grp) ++g1;
-            const bool multi = rows->group_is_list && rows->group_is_list[grp];
-            const bool rev_group = rows->seg_strand[g0] == RCP_STRAND_MINUS;  // strand(x)[1] == "-"
-            const int32_t gfirst = (int32_t)B->segs.size();
-            const int32_t gcount = (int32_t)(g1 - g0);
-            if (gcount > 32767) return fail(RCP_EUNSUPPORTED, "more than 32767 ranges in one mask element");
-            for (int64_t q = 0; q < gcount; ++q) {
-                const int64_t j = rev_group ? (g1 - 1 - q) : (g0 + q);
-                if (rows->seg_chrom[j] != chrom) {
-                    if (multi) return fail(RCP_EUNSUPPORTED, "row %d: mask element spans several chromosomes", r);
-                    return fail(RCP_EUNSUPPORTED, "row %d: groups on different chromosomes", r);
-                }
-                const int32_t s = rows->seg_start[j], e = rows->seg_end[j];
-                RcpSeg sg{};
-                sg.gfirst = gfirst;
-                sg.gcount = (int16_t)gcount;
-                sg.multi = multi ? 1 : 0;
-                sg.group = (uint8_t)grp;
-                sg.streams = stream_mask(rows->ignore_strand, rows->seg_strand[j]);
-                if (e >= s) {
-                    // i2k piece s:e; R drops index 0 and fails on negative indices
-                    if (s < 0) B->row_static[r] = 1;
-                    sg.lo = std::max<int32_t>(s, 1);
-                    sg.hi = e;
-                    sg.query_ok = 1;
-                    sg.rev = rev_group ? 1 : 0;
-                    if (sg.hi < sg.lo) continue;  // only index 0: nothing left
-                } else {
-                    // zero-width range: findOverlaps finds nothing (documented); s:(s-1) still
-                    // yields two positions, which only matters for rows that are NULL anyway
-                    if (multi) return fail(RCP_EUNSUPPORTED, "row %d: zero-width range inside a range list", r);
-                    if (e < 0) B->row_static[r] = 1;
-                    sg.lo = std::max<int32_t>(e, 1);
-                    sg.hi = s;
-                    sg.query_ok = 0;
-                    sg.rev = rev_group ? 0 : 1;
-                    if (sg.hi < sg.lo) continue;
-                }
-                sg.off = off;
-                off += sg.hi - sg.lo + 1;
-                B->segs.push_back(sg);
-            }
-            // fix gcount for skipped empty pieces
-            const int32_t kept = (int32_t)B->segs.size() - gfirst;
-            for (int32_t q = gfirst; q < gfirst + kept; ++q) B->segs[q].gcount = (int16_t)kept;
-            // nearest other ranges of the group (the pileup's one-range weight shortcut)
-            for (int32_t q = gfirst; q < gfirst + kept; ++q) {
-                RcpSeg& a = B->segs[q];
-                a.nb_lo = INT32_MIN;
-                a.nb_hi = INT32_MAX;
-                if (!multi) continue;
-                for (int32_t t = gfirst; t < gfirst + kept; ++t) {
-                    if (t == q || !B->segs[t].query_ok) continue;
-                    const RcpSeg& b = B->segs[t];
-                    if (b.hi < a.lo) a.nb_lo = std::max(a.nb_lo, b.hi);
-                    else if (b.lo > a.hi) a.nb_hi = std::min(a.nb_hi, b.lo);
-                    else a.nb_lo = INT32_MAX;  // intersecting ranges: always count
-                }
-            }
-            g0 = g1;
-        }
-        B->row_len[r] = off;
-    }
-    B->row_seg[R] = (int32_t)B->segs.size();
-    return RCP_OK;
-}
 
 template <class T>
 size_t put(std::vector<char>& blob, const std::vector<T>& v) {
@@ -938,860 +742,7 @@ size_t put(std::vector<char>& blob, const std::vector<T>& v) {
     return off;
 }
 
-// The plan's device tables as one arena: pieces are laid out (256-B aligned) and then copied
-// straight from the host vectors through the pinned staging buffers (rcp_stage.h) -- no host
-// blob to assemble (C4: 26 MB, ~15 ms of host copies and page faults into a fresh vector).
-struct Arena {
-    struct Piece {
-        const void* p;
-        size_t bytes, off;
-    };
-    std::vector<Piece> pieces;
-    size_t total = 0;
-    template <class T>
-    size_t add(const std::vector<T>& v) {
-        const size_t off = (total + 255) & ~size_t(255);
-        if (!v.empty()) pieces.push_back({v.data(), sizeof(T) * v.size(), off});
-        total = off + sizeof(T) * std::max<size_t>(v.size(), 1);
-        return off;
-    }
-    hipError_t upload(void* dev, int device, hipStream_t s) const {
-        for (const Piece& q : pieces) {
-            const hipError_t e = rcp::stage_h2d(static_cast<char*>(dev) + q.off, q.p, q.bytes, device, s);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-};
-
 }  // namespace
-
-extern "C" int rcp_plan_create(const rcp_readset* rs, const rcp_rows_desc* rows, const rcp_bins_desc* bins,
-                               rcp_plan** out) {
-    RCP_TRY
-    return rcp_plan_create_ex(rs, rows, bins, nullptr, out);
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_create_ex(const rcp_readset* rs, const rcp_rows_desc* rows, const rcp_bins_desc* bins,
-                                  const rcp_plan_opts* opts, rcp_plan** out) {
-    RCP_TRY
-    if (!rs || !rows || !out) return fail(RCP_EINVAL, "NULL argument");
-    const rcp_plan_opts default_opts{RCP_KERNEL_AUTO, -1, 0, 0, 0, {0, 0}};
-    if (!opts) opts = &default_opts;
-    if (opts->pileup_kernel < RCP_KERNEL_AUTO || opts->pileup_kernel > RCP_KERNEL_BINS)
-        return fail(RCP_EINVAL, "pileup_kernel = %d", opts->pileup_kernel);
-    if (opts->concurrent < 0) return fail(RCP_EINVAL, "concurrent = %d", opts->concurrent);
-    *out = nullptr;
-    const rcp_bins_desc coverage_only{};  // bins == NULL: a calcCoverage-only plan
-    const bool cov_only = bins == nullptr;
-    if (cov_only) bins = &coverage_only;
-    if (rows->n_rows < 0) return fail(RCP_EINVAL, "n_rows < 0");
-    if (rows->n_rows > 0 && (!rows->seg_off || !rows->seg_chrom || !rows->seg_start || !rows->seg_end || !rows->seg_strand))
-        return fail(RCP_EINVAL, "NULL row array");
-    if (!cov_only && (bins->n_parts < 1 || bins->n_parts > RCP_MAX_PARTS))
-        return fail(RCP_EINVAL, "n_parts = %d", bins->n_parts);
-    if (bins->stat != RCP_STAT_MEAN && bins->stat != RCP_STAT_MEDIAN) return fail(RCP_EINVAL, "stat = %d", bins->stat);
-    if (bins->interp < 0 || bins->interp > 3) return fail(RCP_EINVAL, "interp = %d", bins->interp);
-    const bool rounding = bins->rng_kind == RCP_RNG_ROUNDING;
-    DeviceGuard g(rs->device);
-    HIP_TRY(g.err);
-
-    PlanTimer ptimer;
-    if (!rows->ignore_strand) {  // findOverlaps with strand compatibility: the stranded layout
-        const int rc0 = ensure_stranded(rs);
-        if (rc0) return rc0;
-    } else if (!rs->has_merged) {
-        return fail(RCP_EINVAL, "this readset holds no strand-merged layout (a shard built for ignore.strand = FALSE)");
-    }
-    auto plan = std::make_unique<rcp_plan>();
-    plan->rs = rs;
-    Builder B;
-    int rc = build_rows(rs, rows, &B);
-    if (rc) return rc;
-    const int R = rows->n_rows;
-    PLAN_MARK("build_rows");
-    plan->n_rows = R;
-    plan->n_seg = (int64_t)B.segs.size();
-    plan->row_len.assign(B.row_len.begin(), B.row_len.end());
-    for (int r = 0; r < R; ++r) plan->max_row_len = std::max(plan->max_row_len, B.row_len[r]);
-
-    RcpPlanDev& P = plan->dev;
-    P.multi_rows = 0;
-    for (int r = 0; r < R && !P.multi_rows; ++r) P.multi_rows = B.row_seg[r + 1] - B.row_seg[r] > 1;
-    // persistent pileup grids: all workgroup slots alone, 7/8 beside other samples in flight
-    // (rcp_plan_opts.concurrent; profiles/r04/r4p)
-    P.grid_fill = opts->concurrent > 1 ? 7 : 8;
-    P.n_parts = bins->n_parts;
-    P.stat = bins->stat;
-    P.scale = bins->scale;
-    int64_t col = 0;
-    int32_t chunk_cap = 1024, stage_cap = 1;
-    bool lean_ok = true;  // so far: uniform power-of-two bins (no R-RNG layouts)
-    int32_t max_interp_len = 0, max_interp_bins = 0;
-    std::vector<int32_t> part_max_bin(RCP_MAX_PARTS, 1);
-    std::map<std::pair<int, int>, int32_t> layout_cache;  // (n, dif) -> offset in lay_cnt
-    std::map<std::pair<int, int>, int32_t> nb_cache;      // (n, L) -> offset in nb_pos
-    for (int p = 0; p < bins->n_parts; ++p) {
-        RcpPart& pt = P.part[p];
-        const int32_t f1 = bins->flank[0], f2 = bins->flank[1];
-        if (f1 < 0 || f2 < 0) return fail(RCP_EINVAL, "negative flank");
-        switch (bins->where ? bins->where[p] : RCP_WHERE_WHOLE) {
-            case RCP_WHERE_WHOLE: pt.lo_off = 0; pt.lo_end = 0; pt.hi_off = 0; pt.hi_end = 1; break;
-            case RCP_WHERE_CENTER: pt.lo_off = f1; pt.lo_end = 0; pt.hi_off = -f2; pt.hi_end = 1; break;
-            case RCP_WHERE_UPSTREAM: pt.lo_off = 0; pt.lo_end = 0; pt.hi_off = f1; pt.hi_end = 0; break;
-            case RCP_WHERE_DOWNSTREAM: pt.lo_off = -f2; pt.lo_end = 1; pt.hi_off = 0; pt.hi_end = 1; break;
-            default: return fail(RCP_EINVAL, "where[%d] = %d", p, bins->where[p]);
-        }
-        const int nb = bins->n_bins[p];
-        if (nb < 0) return fail(RCP_EINVAL, "n_bins[%d] < 0", p);
-        pt.per_base = nb == 0;
-        pt.n_bins = pt.per_base ? (bins->per_base_width ? bins->per_base_width[p] : 0) : nb;
-        if (pt.n_bins <= 0) return fail(RCP_EINVAL, "part %d has no columns", p);
-        pt.col_off = (int32_t)col;
-        col += pt.n_bins;
-        pt.lay_base = (int32_t)B.lay_index.size();
-        int32_t max_bin = 1;
-        if (!pt.per_base) {
-            B.lay_index.resize(B.lay_index.size() + pt.n_bins, -1);
-            for (int r = 0; r < R; ++r) {
-                int32_t head, L;
-                rcp_part_slice(pt, B.row_len[r], &head, &L);
-                if (B.row_static[r] || B.row_seg[r] == B.row_seg[r + 1]) continue;  // always NULL
-                if (L < 0 || head < 0 || head + L > B.row_len[r])
-                    return fail(RCP_EUNSUPPORTED, "row %d: part %d slice out of its %d-long coverage", r, p,
-                                B.row_len[r]);
-                if (L < pt.n_bins) {
-                    int mode = bins->interp;
-                    if (mode == RCP_INTERP_AUTO)
-                        mode = ((double)(pt.n_bins - L) / pt.n_bins < 0.2) ? RCP_INTERP_NEIGHBORHOOD : RCP_INTERP_SPLINE;
-                    int32_t pos_off = -1;
-                    if (mode == RCP_INTERP_NEIGHBORHOOD) {
-                        auto key = std::make_pair(pt.n_bins, L);
-                        auto it = nb_cache.find(key);
-                        if (it == nb_cache.end()) {
-                            std::vector<int32_t> pos;
-                            if (!rcp::neighborhood_positions(pt.n_bins, L, rounding, &pos))
-                                return fail(RCP_ESEMANTIC,
-                                            "splitVector neighborhood interpolation of %d values into %d bins: R raises an error",
-                                            L, pt.n_bins);
-                            pos_off = (int32_t)B.nb_pos.size();
-                            B.nb_pos.insert(B.nb_pos.end(), pos.begin(), pos.end());
-                            nb_cache[key] = pos_off;
-                        } else {
-                            pos_off = it->second;
-                        }
-                    } else if (mode == RCP_INTERP_SPLINE && L < 1) {
-                        return fail(RCP_ESEMANTIC, "spline() of zero points: R raises an error");
-                    } else if (mode == RCP_INTERP_LINEAR && L < 1) {
-                        return fail(RCP_EUNSUPPORTED, "empty slice with the 'linear' interpolation");
-                    }
-                    B.interp_row.push_back(r);
-                    B.interp_part.push_back(p);
-                    B.interp_mode.push_back(mode);
-                    B.interp_pos.push_back(pos_off);
-                    max_interp_len = std::max(max_interp_len, L);
-                    max_interp_bins = std::max(max_interp_bins, pt.n_bins);
-                    continue;
-                }
-                const int32_t bs = L / pt.n_bins;
-                const int32_t dif = L - bs * pt.n_bins;
-                if (dif || (bs & (bs - 1))) lean_ok = false;
-                // median bins wider than a wave chunk go to the slow-row kernel (mode 4) and do
-                // not size the chunks of the others
-                if (bins->stat != RCP_STAT_MEDIAN || bs + (dif ? 1 : 0) < kWaveMax)
-                    max_bin = std::max(max_bin, bs + (dif ? 1 : 0));
-                if (dif) {
-                    int32_t& slot = B.lay_index[pt.lay_base + dif];
-                    if (slot < 0) {
-                        auto key = std::make_pair(pt.n_bins, dif);
-                        auto it = layout_cache.find(key);
-                        if (it == layout_cache.end()) {
-                            const std::vector<int32_t> cnt = rcp::bin_layout_counts(pt.n_bins, dif, rounding);
-                            const int32_t o = (int32_t)B.lay_cnt.size();
-                            B.lay_cnt.insert(B.lay_cnt.end(), cnt.begin(), cnt.end());
-                            B.lay_regions.emplace_back(o, pt.n_bins);
-                            layout_cache[key] = o;
-                            slot = o;
-                        } else {
-                            slot = it->second;
-                        }
-                    }
-                }
-            }
-        }
-        part_max_bin[p] = max_bin;
-    }
-    if (max_interp_len > kChunkMax)
-        return fail(RCP_EUNSUPPORTED, "interpolated slice of %d positions exceeds %d", max_interp_len, kChunkMax);
-
-    // ---- geometry.  A workgroup handles <= kStageMaxBins bins of a part for 32 rows; a wave
-    // piles a row's positions for those bins in sub-chunks of at most `chunk_cap` positions
-    // (bins straddling sub-chunks accumulate).  Pick the largest wave chunk (<= kWaveMax) whose
-    // LDS (4 wave arrays + [bin][row] stage + row metadata) keeps two workgroups per CU.
-    {
-        const bool median = bins->stat == RCP_STAT_MEDIAN;
-        int32_t need = 64;
-        for (int p = 0; p < P.n_parts; ++p) {
-            RcpPart& pt = P.part[p];
-            // equal chunks of at most kStageMaxBins bins
-            int32_t nch = (pt.n_bins + kStageMaxBins - 1) / kStageMaxBins;
-            int32_t cb = (pt.n_bins + nch - 1) / nch;
-            // wide binned chunks would be piled in several wave sub-chunks, each streaming the
-            // chunk's reads again: split them into more (up to 8) column chunks instead -- more
-            // workgroups for small row counts, and per-chunk read ranges from locate.  The general
-            // kernel's cap stays at the 8 chunks its A/B measured (lean plans split further, to
-            // RCP_MAX_CRANGE_CHUNKS, below)
-            const int32_t pos_max = 1023;
-            if (!median && !pt.per_base && part_max_bin[p] > 0 && (int64_t)cb * part_max_bin[p] > pos_max) {
-                const int32_t cb2 = std::max<int32_t>(1, pos_max / part_max_bin[p]);
-                const int32_t nch2 = (pt.n_bins + cb2 - 1) / cb2;
-                if (nch2 <= kGeneralMaxChunks) {
-                    nch = nch2;
-                    cb = (pt.n_bins + nch - 1) / nch;
-                }
-            }
-            // opts->min_col_chunks (one-part plans): at least that many column chunks
-            if (!median && P.n_parts == 1 && opts->min_col_chunks > nch) {
-                nch = std::min<int32_t>(std::min(opts->min_col_chunks, RCP_MAX_CRANGE_CHUNKS), pt.n_bins);
-                cb = (pt.n_bins + nch - 1) / nch;
-            }
-            if (median) cb = std::min<int32_t>(cb, std::max<int32_t>(1, kWaveMax / part_max_bin[p]));
-            pt.chunk_bins = cb;
-            pt.n_chunks = (pt.n_bins + cb - 1) / cb;
-            stage_cap = std::max(stage_cap, cb);
-            need = std::max<int64_t>(need, std::min<int64_t>((int64_t)cb * part_max_bin[p], kWaveMax));
-        }
-        if (cov_only) need = std::max(need, std::min(plan->max_row_len, kWaveMax));
-        int32_t min_cap = 64;
-        if (median)
-            for (int p = 0; p < P.n_parts; ++p) min_cap = std::max(min_cap, P.part[p].chunk_bins * part_max_bin[p]);
-        const int32_t cands[] = {need, 2047, 1023, 511};  // 64 * 2^k - 1: the +1 sentinel fits
-        chunk_cap = -1;
-        for (int32_t ch : cands) {
-            if (ch > need || ch < min_cap) continue;
-            RcpPlanDev t{};
-            int32_t cap_unused = 0;
-            wave_geometry(ch, &t.wave_words, &cap_unused);
-            t.stage_cap = cov_only ? 0 : stage_cap;
-            chunk_cap = ch;
-            if (rcp_pileup_lds_bytes(&t, cov_only ? 1 : 0) <= kLdsBudget) break;
-        }
-        if (chunk_cap < 0) chunk_cap = need;
-    }
-    P.n_cols = col;
-    plan->n_cols = col;
-    if (opts->out_ld == RCP_OUT_LD_PADDED) P.out_ld = ((int64_t)R + 15) & ~int64_t(15);
-    else if (opts->out_ld == 0) P.out_ld = R;
-    else if (opts->out_ld >= R) P.out_ld = opts->out_ld;
-    else return fail(RCP_EINVAL, "out_ld = %lld < n_rows = %d", (long long)opts->out_ld, R);
-    plan->out_ld = P.out_ld;
-    wave_geometry(chunk_cap, &P.wave_words, &P.chunk_cap);
-    P.stage_cap = stage_cap;
-    P.interp_cap = std::max(max_interp_len, 1);
-    if (bins->stat == RCP_STAT_MEDIAN) {
-        // rows whose median bins exceed the wave chunk: block-level windows (mode 4)
-        for (int p = 0; p < P.n_parts; ++p) {
-            const RcpPart& pt = P.part[p];
-            if (pt.per_base) continue;
-            for (int r = 0; r < R; ++r) {
-                if (B.row_static[r] || B.row_seg[r] == B.row_seg[r + 1]) continue;
-                int32_t head, L;
-                rcp_part_slice(pt, B.row_len[r], &head, &L);
-                if (L < pt.n_bins) continue;
-                const int32_t bs = L / pt.n_bins, dif = L - bs * pt.n_bins;
-                const int32_t w = bs + (dif ? 1 : 0);
-                if (w <= P.chunk_cap) continue;
-                if (w > kChunkMax)
-                    return fail(RCP_EUNSUPPORTED, "row %d: a median bin of %d positions exceeds %d", r, w, kChunkMax);
-                B.interp_row.push_back(r);
-                B.interp_part.push_back(p);
-                B.interp_mode.push_back(4);
-                B.interp_pos.push_back(dif ? B.lay_index[pt.lay_base + dif] : -1);
-                P.interp_cap = std::max(P.interp_cap, w);
-            }
-        }
-    }
-    P.n_chunks_total = 0;
-    for (int p = 0; p < P.n_parts; ++p) P.n_chunks_total += P.part[p].n_chunks;
-
-    // ---- lean pileup kernel: every row one plain range (no exon list, no zero-width query),
-    // mean of uniform power-of-two bins, each chunk inside one wave's fused pass (<= 1023
-    // positions) and the stage inside the store waves' registers
-    // With opts->pileup_kernel == RCP_KERNEL_LEAN_ANY, other plans take its general-bins mode
-    // (lean == 2): any uniform width, R-RNG layouts and multi-range rows, as long as every chunk
-    // is one wave's pass (no sub-chunks) and holds <= rcp_lean_gen_max_bins() bins.  Measured
-    // slower than the general kernel on C2 (0.082 vs 0.063 ms) and C3 (0.96 vs 0.88 ms), so
-    // AUTO does not choose it.  RCP_KERNEL_GENERAL keeps every plan on the general kernel.
-    bool lean_base = false;  // a lean plan whose every part is per base
-    {
-        const int kind = opts->pileup_kernel;
-        bool base = !cov_only && bins->stat == RCP_STAT_MEAN && P.chunk_cap <= 1023 && kind != RCP_KERNEL_GENERAL;
-        for (int p = 0; base && p < P.n_parts; ++p) {
-            const RcpPart& pt = P.part[p];
-            const int64_t w = pt.per_base ? 1 : part_max_bin[p];
-            if ((int64_t)pt.chunk_bins * w > P.chunk_cap) base = false;
-        }
-        bool lean = base && lean_ok && stage_cap <= rcp_lean_max_bins();
-        if (lean && kind == RCP_KERNEL_AUTO && R < kLeanMinRowsBinned) {
-            bool binned = true;
-            for (int p = 0; p < P.n_parts; ++p) binned = binned && !P.part[p].per_base;
-            if (binned) lean = false;
-        }
-        for (int r = 0; lean && r < R; ++r) {
-            const int32_t j0 = B.row_seg[r], j1 = B.row_seg[r + 1];
-            if (j1 - j0 > 1) lean = false;
-            else if (j1 == j0 + 1 && (B.segs[j0].multi || !B.segs[j0].query_ok)) lean = false;
-        }
-        const bool gen = !lean && base && kind == RCP_KERNEL_LEAN_ANY &&
-                         stage_cap <= rcp_lean_gen_max_bins();
-        P.lean = lean ? 1 : (gen ? 2 : 0);
-        {
-            bool per_base = true;
-            for (int p = 0; p < P.n_parts; ++p) per_base = per_base && P.part[p].per_base;
-            lean_base = P.lean && per_base;
-            P.lean_rounds = lean_base ? 2 : 0;
-            // (RCP_LEAN_ROUNDS=2: diagnostics A/B of two-round items for binned lean plans)
-            if (P.lean && !per_base && std::getenv("RCP_LEAN_ROUNDS") && std::atoi(std::getenv("RCP_LEAN_ROUNDS")) == 2)
-                P.lean_rounds = 2;
-        }
-        // row-wave kernel (lean == 3): mean bins of any layout, every bin inside one window;
-        // AUTO takes it for plans with multi-range rows (coverageRnaRef, genebody + flanks)
-        bool rows_ok = !cov_only && bins->stat == RCP_STAT_MEAN && kind != RCP_KERNEL_GENERAL && !lean;
-        for (int p = 0; rows_ok && p < P.n_parts; ++p)
-            if (!P.part[p].per_base && part_max_bin[p] > rcp_rows_window_cap()) rows_ok = false;
-        bool multi_rows = false;
-        for (int r = 0; !multi_rows && r < R; ++r) multi_rows = B.row_seg[r + 1] - B.row_seg[r] > 1;
-        if (rows_ok && (kind == RCP_KERNEL_ROWS || (kind == RCP_KERNEL_AUTO && multi_rows))) {
-            P.lean = 3;
-            // each wave searches its rows' (segment, stream) ranges itself (no locate launch, no
-            // 64-B record round trip; a skewed row stays with the wave that claimed it) unless
-            // the caller asked for the heavy path
-            P.fold = opts->heavy_threshold <= 0 ? 1 : 0;
-        }
-    }
-    // ---- bin-difference kernel (lean == 4): mean plans of one binned part whose rows are
-    // single ranges, every row's slice a whole number of bins of >= rcp_bins_min_width()
-    // positions (no splitVector layout, no interpolation), <= rcp_bins_max_bins() bins.  A row
-    // is one wave's pass over its bins (no column chunks).  AUTO takes it for such plans:
-    // C2 (200 bins of 20 bp) ... ; RCP_KERNEL_BINS forces it where the shape allows
-    {
-        const int kind = opts->pileup_kernel;
-        bool bd = !cov_only && bins->stat == RCP_STAT_MEAN && P.n_parts == 1 && !P.part[0].per_base &&
-                  P.part[0].n_bins > 0 && P.part[0].n_bins <= rcp_bins_max_bins() &&
-                  (kind == RCP_KERNEL_AUTO || kind == RCP_KERNEL_BINS);
-        const RcpPart& pt0 = P.part[0];
-        for (int r = 0; bd && r < R; ++r) {
-            const int32_t j0 = B.row_seg[r], j1 = B.row_seg[r + 1];
-            if (B.row_static[r] || j1 == j0) continue;  // NULL rows: zeros
-            if (j1 - j0 > 1 || B.segs[j0].multi || !B.segs[j0].query_ok) {
-                bd = false;
-                break;
-            }
-            int32_t head, L;
-            rcp_part_slice(pt0, B.row_len[r], &head, &L);
-            if (L < pt0.n_bins || L % pt0.n_bins != 0 || L / pt0.n_bins < rcp_bins_min_width()) bd = false;
-        }
-        if (bd && B.interp_row.empty()) {
-            P.lean = 4;
-            P.part[0].chunk_bins = P.part[0].n_bins;
-            P.part[0].n_chunks = 1;
-            P.n_chunks_total = 1;
-            P.stage_cap = P.part[0].n_bins;
-            // the kernel searches its rows' read ranges itself (the locate and heavy launches
-            // were as long as the pileup on C2) unless the caller asked for the heavy path
-            P.fold = opts->heavy_threshold <= 0 ? 1 : 0;
-        }
-    }
-    // ---- general-kernel plans of small tables of single ranges in the merged layout (one GPU's
-    // shard of a peak table: C4 1/8 spent locate 25 + heavy 8 us ahead of a 93-us pileup): the
-    // pileup kernel searches each row's and chunk's read ranges itself (fold_row) and piles a
-    // skewed row with the whole workgroup instead of heavy slices -- unless the caller asked for
-    // the heavy path.  Every chunk must be one wave pass (no sub-chunks: those read locate's
-    // segment ranges) and no row interpolated (rcp_interp_kernel reads them too)
-    if (P.lean == 0 && !cov_only && rows->ignore_strand && opts->heavy_threshold <= 0 && B.interp_row.empty() &&
-        R > 0 && R <= kFoldMaxRows) {
-        bool f = true;
-        for (int p = 0; f && p < P.n_parts; ++p) {
-            const RcpPart& pt = P.part[p];
-            const int64_t w = pt.per_base ? 1 : part_max_bin[p];
-            if ((int64_t)pt.chunk_bins * w > P.chunk_cap) f = false;
-        }
-        for (int r = 0; f && r < R; ++r) {
-            const int32_t j0 = B.row_seg[r], j1 = B.row_seg[r + 1];
-            if (B.row_static[r] || j1 == j0) continue;  // NULL rows
-            if (j1 - j0 > 1 || B.segs[j0].multi || !B.segs[j0].query_ok) f = false;
-        }
-        P.fold = f ? 1 : 0;
-    }
-    // ---- per-base lean plans of small tables in the merged layout (one GPU's shard of a per-base
-    // table: C5 1/8 spent locate 45 us ahead of a 143-us pileup): the store wave that claims an
-    // item searches its rows' read ranges while the pile waves work on the previous item -- no
-    // locate launch.  (Binned lean plans keep the locate: their skewed rows need the heavy slices.)
-    // Plans built for several samples in flight (rcp_plan_opts.concurrent) of a larger table keep
-    // the locate launch: it runs beside another sample's pileup there, while the claim's searches
-    // lengthen this kernel (full C5 at D = 2: 0.459-0.463 vs 0.472-0.480 ms a step).
-    if (P.lean == 1 && lean_base && rows->ignore_strand && opts->heavy_threshold <= 0 &&
-        B.interp_row.empty() && R > 0 && R <= kFoldMaxRows && (opts->concurrent <= 1 || R <= kFoldConcurrentMaxRows) &&
-        !std::getenv("RCP_NO_LEAN_FOLD")) {
-        bool f = true;
-        for (int r = 0; f && r < R; ++r) {
-            const int32_t j0 = B.row_seg[r], j1 = B.row_seg[r + 1];
-            if (B.row_static[r] || j1 == j0) continue;
-            if (j1 - j0 > 1 || B.segs[j0].multi || !B.segs[j0].query_ok) f = false;
-        }
-        P.fold = f ? 1 : 0;
-    }
-    // (RCP_COOP_MIN: diagnostics A/B of the cooperative rows' threshold)
-    P.coop_min = std::getenv("RCP_COOP_MIN") ? std::max(0, std::atoi(std::getenv("RCP_COOP_MIN"))) : kCoopMin;
-    // ---- lean plans with few row tiles (one GPU's shard of a region table): the persistent
-    // grid (two workgroups per CU) takes (row tile, column chunk) items; with few items per
-    // workgroup the last ones leave most workgroups idle, so cut the parts into more column
-    // chunks (each streams only its reads: crange) until there are >= kLeanItemsPerWg per
-    // workgroup, or opts->min_col_chunks asks for more
-    if (P.lean == 1 && R > 0) {
-        int cus = 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, rs->device) != hipSuccess || cus <= 0)
-            cus = 256;
-        const int64_t grid = (2 * (int64_t)cus + 7) / 8 * 8;
-        const int64_t trows = P.lean_rounds == 2 ? 32 : rcp_tile_rows();
-        const int64_t tiles = ((int64_t)R + trows - 1) / trows;
-        auto can_split = [&]() {
-            if (P.n_chunks_total * 2 > RCP_MAX_CRANGE_CHUNKS) return false;
-            for (int p = 0; p < P.n_parts; ++p)
-                if (P.part[p].chunk_bins < 2 * kLeanMinChunkBins) return false;
-            return true;
-        };
-        auto split = [&]() {
-            P.n_chunks_total = 0;
-            for (int p = 0; p < P.n_parts; ++p) {
-                RcpPart& pt = P.part[p];
-                const int32_t nch = 2 * pt.n_chunks;
-                pt.chunk_bins = (pt.n_bins + nch - 1) / nch;
-                pt.n_chunks = (pt.n_bins + pt.chunk_bins - 1) / pt.chunk_bins;
-                P.n_chunks_total += pt.n_chunks;
-            }
-        };
-        const int64_t want = (lean_base ? kLeanItemsPerWgBase : kLeanItemsPerWg) * grid;
-        while (can_split() && (tiles * P.n_chunks_total < want || P.n_chunks_total < opts->min_col_chunks))
-            split();
-        P.stage_cap = 1;
-        for (int p = 0; p < P.n_parts; ++p) P.stage_cap = std::max(P.stage_cap, P.part[p].chunk_bins);
-    }
-
-    PLAN_MARK("parts+geometry");
-    // ---- skewed rows: heavy slots sized for the eligible (short enough) rows
-    const int32_t heavy_thr = opts->heavy_threshold < 0 ? kHeavyThreshold : opts->heavy_threshold;
-    int32_t eligible_len = 0;
-    for (int r = 0; r < R; ++r)
-        if (B.row_len[r] <= kHeavyMaxLen) eligible_len = std::max(eligible_len, B.row_len[r]);
-    P.heavy_threshold = heavy_thr;
-    P.heavy_max_len = eligible_len;
-    P.heavy_stride = ((eligible_len + 1) + 63) & ~63;
-    P.heavy_slice = kHeavySlice;
-    P.heavy_cap = (int32_t)std::min<int64_t>(std::max(R, 1), std::min<int64_t>(4096, (256ll << 20) / (4ll * P.heavy_stride)));
-    if (heavy_thr <= 0 || R == 0 || P.fold) P.heavy_threshold = 0;
-
-    // ---- upload tables (one arena)
-    Arena blob;
-    const size_t o_row_chrom = blob.add(B.row_chrom);
-    const size_t o_row_seg = blob.add(B.row_seg);
-    const size_t o_row_len = blob.add(B.row_len);
-    const size_t o_row_static = blob.add(B.row_static);
-    const size_t o_segs = blob.add(B.segs);
-    const size_t o_lay_index = blob.add(B.lay_index);
-    const size_t o_lay_cnt = blob.add(B.lay_cnt);
-    // the same layouts as bit masks (word lay + j: bins 32 j .. 32 j + 31 enlarged), indexed
-    // like lay_cnt: one load per 32 bins where the row-wave flush needs the bin widths
-    std::vector<uint32_t> lay_bit(B.lay_cnt.size(), 0u);
-    for (const auto& rg : B.lay_regions)
-        for (int32_t k = 0; k < rg.second; ++k)
-            if (B.lay_cnt[rg.first + k + 1] != B.lay_cnt[rg.first + k]) lay_bit[rg.first + (k >> 5)] |= 1u << (k & 31);
-    const size_t o_lay_bit = blob.add(lay_bit);
-    const size_t o_irow = blob.add(B.interp_row);
-    const size_t o_ipart = blob.add(B.interp_part);
-    const size_t o_imode = blob.add(B.interp_mode);
-    const size_t o_ipos = blob.add(B.interp_pos);
-    // row-wave plans interpolate the rows they pile (rcp_pileup_rows_kernel): entry of (row, part)
-    std::vector<int32_t> interp_of;
-    if (P.lean == 3 && !B.interp_row.empty()) {
-        interp_of.assign((size_t)R * P.n_parts, -1);
-        for (size_t e = 0; e < B.interp_row.size(); ++e)
-            interp_of[(size_t)B.interp_row[e] * P.n_parts + B.interp_part[e]] = (int32_t)e;
-    }
-    const size_t o_iof = blob.add(interp_of);
-    // ... and claim the 16-row tiles holding such rows first, most first: the spline's serial
-    // chains then run beside the other waves' pileup, not in the grid's tail
-    std::vector<int32_t> tile_perm;
-    if (!interp_of.empty()) {
-        const int32_t n_tiles = (R + 15) / 16;
-        std::vector<int32_t> cnt(n_tiles, 0);
-        for (int32_t r : B.interp_row) ++cnt[r / 16];
-        tile_perm.resize(n_tiles);
-        for (int32_t t = 0; t < n_tiles; ++t) tile_perm[t] = t;
-        std::stable_sort(tile_perm.begin(), tile_perm.end(), [&](int32_t a, int32_t b) { return cnt[a] > cnt[b]; });
-    }
-    const size_t o_tperm = blob.add(tile_perm);
-    const size_t o_nb = blob.add(B.nb_pos);
-    // locate's per-row input (RcpRowInfo)
-    std::vector<RcpRowInfo> row_info((size_t)std::max(R, 1));
-    {
-        const ReadLayout& RL0 = rows->ignore_strand ? rs->merged : rs->stranded;
-        for (int r = 0; r < R; ++r) {
-            RcpRowInfo& ri = row_info[r];
-            std::memset(&ri, 0, sizeof(ri));
-            ri.j0 = B.row_seg[r];
-            ri.j1 = B.row_seg[r + 1];
-            ri.chrom = B.row_chrom[r];
-            ri.row_len = B.row_len[r];
-            ri.stat = B.row_static[r];
-            const bool cok = ri.chrom >= 0 && ri.chrom < rs->n_chrom;
-            ri.seqlen = cok ? rs->seqlen[ri.chrom] : -1;
-            if (cok) {
-                ri.d0 = RL0.h_dir_off[(size_t)ri.chrom * 3];
-                ri.nb = (int32_t)(RL0.h_dir_off[(size_t)ri.chrom * 3 + 1] - ri.d0) - 1;
-            }
-            if (ri.j1 > ri.j0) ri.seg0 = B.segs[ri.j0];
-        }
-    }
-    const size_t o_rinfo = blob.add(row_info);
-    // fmm pivots (see RcpPlanDev::spl_tb): the elimination of R's fmm_spline with d[i] = 1
-    std::vector<double> spl_tb(2 * ((size_t)std::max(max_interp_len, 1) + 1), 0.0);
-    {
-        double bp = -1.0;
-        spl_tb[1] = bp;
-        for (size_t i = 1; 2 * i + 1 < spl_tb.size(); ++i) {
-            const double t = 1.0 / bp;
-            bp = 4.0 - t;
-            spl_tb[2 * i] = t;
-            spl_tb[2 * i + 1] = bp;
-        }
-    }
-    const size_t o_spl = blob.add(spl_tb);
-    PLAN_MARK("tables (host)");
-    HIP_TRY(plan->tables.alloc(blob.total, nullptr));
-    HIP_TRY(blob.upload(plan->tables.p, rs->device, nullptr));
-    PLAN_MARK("tables upload");
-    char* base = plan->tables.as<char>();
-    // ---- work arena: locate outputs, heavy-row state, status words
-    const int64_t S = std::max<int64_t>(plan->n_seg, 1);
-    const int64_t Rw = std::max(R, 1);
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t w_lo = 0;
-    const size_t w_hi = al(w_lo + 12 * S);
-    const size_t w_valid = al(w_hi + 12 * S);
-    const size_t w_ncand = al(w_valid + Rw);
-    const size_t w_hrows = al(w_ncand + 4 * Rw);
-    const size_t w_hoff = al(w_hrows + 4 * (size_t)P.heavy_cap);
-    const size_t w_gdiff = al(w_hoff + 4 * ((size_t)P.heavy_cap + 1));
-    const size_t w_rec = al(w_gdiff + (P.heavy_threshold > 0 ? 4 * (size_t)P.heavy_cap * P.heavy_stride : 0));
-    const bool keep_crange = P.n_chunks_total > 1 && P.n_chunks_total <= RCP_MAX_CRANGE_CHUNKS;
-    const size_t w_crange = al(w_rec + sizeof(RcpRowRec) * Rw);
-    // heaviest-first lean items (rcp_device.h lpt): per-base lean plans of few 32-row items,
-    // i.e. one GPU's shard of a per-base table (C5 1/8: TSS windows' middle column chunks hold
-    // several times the outer chunks' reads; in per-XCD order a workgroup that drew two heavy
-    // items sets the pass)
-    const int64_t lpt_items = ((int64_t)R + 31) / 32 * P.n_chunks_total;
-    int lpt_cus = 256;
-    if (hipDeviceGetAttribute(&lpt_cus, hipDeviceAttributeMultiprocessorCount, rs->device) != hipSuccess || lpt_cus <= 0)
-        lpt_cus = 256;
-    // (a full per-base table, e.g. C5's 6256 items, keeps the per-XCD order and its L2 locality)
-    P.lpt = P.lean == 1 && lean_base && keep_crange && R > 0 && !P.fold &&
-            lpt_items <= (int64_t)kLeanItemsPerWgBase * 2 * lpt_cus;
-    P.lpt_cap = P.lpt ? (int32_t)lpt_items : 0;
-    const size_t w_order = al(w_crange + (keep_crange ? sizeof(uint2) * 3 * (size_t)P.n_chunks_total * Rw : 0));
-    const size_t w_status = al(w_order + 4 * (size_t)RCP_LPT_CLASSES * (size_t)P.lpt_cap);
-    static_assert(2 * RCP_STATUS_WORDS * 4 <= 256, "two status sets");
-    HIP_TRY(plan->work.alloc(w_status + 256, nullptr));
-    PLAN_MARK("work alloc");
-    char* wb = plan->work.as<char>();
-    P.ncand = reinterpret_cast<uint32_t*>(wb + w_ncand);
-    P.heavy_rows = reinterpret_cast<int32_t*>(wb + w_hrows);
-    P.heavy_nslice = reinterpret_cast<uint32_t*>(wb + w_hoff);
-    P.heavy_gdiff = reinterpret_cast<int32_t*>(wb + w_gdiff);
-    P.rec = reinterpret_cast<RcpRowRec*>(wb + w_rec);
-    P.crange = keep_crange ? reinterpret_cast<uint2*>(wb + w_crange) : nullptr;
-    P.item_order = P.lpt ? reinterpret_cast<int32_t*>(wb + w_order) : nullptr;
-    // the locate kernel's chunk windows for the rows of the first row's length (all rows of
-    // C2 / C4 / C5), when no part of that length has an R-RNG layout: the same arithmetic as
-    // the kernel's chunk_window, once per plan instead of once per (row, chunk)
-    P.cw_len = -1;
-    if (keep_crange && R > 0) {
-        const int32_t nr = B.row_len[0];
-        bool ok = true;
-        int c = 0;
-        for (int p = 0; ok && p < P.n_parts; ++p) {
-            const RcpPart& pt = P.part[p];
-            for (int cp = 0; cp < pt.n_chunks; ++cp, ++c) {
-                int32_t head, L;
-                rcp_part_slice(pt, nr, &head, &L);
-                const int32_t n = pt.n_bins, k0 = cp * pt.chunk_bins;
-                P.cw[2 * c] = 0;
-                P.cw[2 * c + 1] = -1;
-                if (k0 >= n || (pt.per_base ? L != n : L < n)) continue;
-                const int32_t bs = pt.per_base ? 1 : L / n;
-                if (!pt.per_base && L - bs * n != 0) {
-                    ok = false;  // an R-RNG layout: the kernel computes these rows itself
-                    break;
-                }
-                if (P.stat == 1 && bs > P.chunk_cap) continue;
-                const int32_t kend = std::min(k0 + pt.chunk_bins, n);
-                P.cw[2 * c] = head + bs * k0;
-                P.cw[2 * c + 1] = bs * (kend - k0);
-            }
-        }
-        if (ok) P.cw_len = nr;
-    }
-    const int32_t n_interp = (int32_t)B.interp_row.size();
-    // x (L+1) | b, c, d (3 (L+1)) for the spline, or the neighborhood fill's n pre-fill values
-    P.interp_stride = (max_interp_len + 1) + std::max(max_interp_bins, 3 * (max_interp_len + 1)) + 8;
-    if (n_interp) HIP_TRY(plan->scratch.alloc(8 * (size_t)n_interp * P.interp_stride, nullptr));
-
-    const ReadLayout& RL = rows->ignore_strand ? rs->merged : rs->stranded;
-    P.se = RL.se.as<int2>();
-    // uniform-width reads: the general kernel and per-base lean plans stream the starts alone;
-    // binned lean plans keep the (start, end) pairs -- C4's latency-bound pile measured 4 % slower
-    // with starts (pileup 0.578 vs 0.555 ms, same box), C5's dense per-base rows 6 % faster
-    // (0.58 vs 0.62), the 1/8 C4 shard's general kernel 4 % (profiles/r03/pipeline/general_starts_ab.log,
-    // lean_starts_c4_ab.log)
-    const bool use_st = RL.st.p && (P.lean != 1 || lean_base);
-    P.st = use_st ? RL.st.as<int32_t>() : nullptr;
-    P.st_w = RL.st_w;
-    P.pmax = RL.pmax.as<int32_t>();
-    P.stream_off = RL.stream_off.as<int64_t>();
-    P.seqlen = rs->d_seqlen.as<int64_t>();
-    P.dir_l = RL.dir_l.as<int32_t>();
-    P.dir_u = RL.dir_l.as<int32_t>() + 1;  // interleaved with dir_l (stride 2)
-    P.dir_off = RL.dir_off.as<int64_t>();
-    P.dir_k = RL.dir_k.as<int32_t>();
-    P.dir_shift = RL.dir_shift;
-    P.merged = rows->ignore_strand ? 1 : 0;
-    P.n_chrom = rs->n_chrom;
-    P.n_rows = R;
-    P.row_chrom = reinterpret_cast<const int32_t*>(base + o_row_chrom);
-    P.row_seg = reinterpret_cast<const int32_t*>(base + o_row_seg);
-    P.row_len = reinterpret_cast<const int32_t*>(base + o_row_len);
-    P.row_static = reinterpret_cast<const uint8_t*>(base + o_row_static);
-    P.segs = reinterpret_cast<const RcpSeg*>(base + o_segs);
-    P.row_info = reinterpret_cast<const RcpRowInfo*>(base + o_rinfo);
-    P.seg_lo = reinterpret_cast<uint32_t*>(wb + w_lo);
-    P.seg_hi = reinterpret_cast<uint32_t*>(wb + w_hi);
-    P.valid = reinterpret_cast<uint8_t*>(wb + w_valid);
-    plan->status_sets = reinterpret_cast<uint32_t*>(wb + w_status);
-    P.status = plan->status_sets;  // set by begin_exec per execution
-    P.status_prev = plan->status_sets + RCP_STATUS_WORDS;
-    P.lay_index = reinterpret_cast<const int32_t*>(base + o_lay_index);
-    P.lay_cnt = reinterpret_cast<const int32_t*>(base + o_lay_cnt);
-    P.lay_bit = reinterpret_cast<const uint32_t*>(base + o_lay_bit);
-    P.n_interp = n_interp;
-    P.interp_row = reinterpret_cast<const int32_t*>(base + o_irow);
-    P.interp_part = reinterpret_cast<const int32_t*>(base + o_ipart);
-    P.interp_mode = reinterpret_cast<const int32_t*>(base + o_imode);
-    P.interp_pos = reinterpret_cast<const int32_t*>(base + o_ipos);
-    P.interp_of = interp_of.empty() ? nullptr : reinterpret_cast<const int32_t*>(base + o_iof);
-    P.tile_perm = tile_perm.empty() ? nullptr : reinterpret_cast<const int32_t*>(base + o_tperm);
-    P.nb_pos = reinterpret_cast<const int32_t*>(base + o_nb);
-    P.spl_tb = reinterpret_cast<const double*>(base + o_spl);
-    P.interp_scratch = plan->scratch.as<double>();
-    P.csr_off = nullptr;
-    P.csr_out = nullptr;
-    P.csr_rs = nullptr;
-    P.csr_sub = nullptr;
-    P.csr_sub_off = nullptr;
-    // row-wave plans whose tile stage does not fit LDS stage their bin numerators row-major
-    // (uint32 numerators, divided at the flush)
-    P.rm32 = nullptr;
-    P.rinfo = nullptr;
-    if (P.lean == 3 && R > 0 && P.n_cols > 0) {
-        HIP_TRY(plan->rm.alloc(4 * (size_t)R * (size_t)P.n_cols + 8 * (size_t)R * RCP_MAX_PARTS, nullptr));
-        P.rinfo = plan->rm.as<int2>();
-        P.rm32 = reinterpret_cast<uint32_t*>(P.rinfo + (size_t)R * RCP_MAX_PARTS);
-    }
-    plan->lds = P.lean == 4 ? rcp_pileup_bins_lds_bytes(&P)
-                : P.lean == 3 ? rcp_pileup_rows_lds_bytes(&P)
-                              : (P.lean ? rcp_pileup_lean_lds_bytes(&P) : rcp_pileup_lds_bytes(&P, cov_only ? 1 : 0));
-    // the row-wave kernel's persistent grid holds one workgroup per CU for the whole pass: the
-    // interpolation rows (a side stream, forked after locate) fit beside it only in the LDS it
-    // leaves -- their spline arrays then go to global scratch (C3: 148 KB + 4 KB, vs 20 KB that
-    // waited for the pileup to end)
-    P.interp_lds_budget = P.lean == 3 ? (int32_t)std::max<int64_t>(0, 160 * 1024 - (int64_t)plan->lds) : 0;
-    // general kernel: 2 rounds (32 rows) per workgroup (C3: 0.88 ms vs 0.91 with 4 rounds, 0.89
-    // with 1), 1 when the row table is small, so that the grid still holds two workgroups per
-    // CU (C2: 10k rows -> 625 workgroups instead of 157; pileup 0.076 -> 0.063 ms)
-    {
-        int tile = 16, rmax = 4;
-        rcp_tile_geometry(&tile, &rmax);
-        int cus = 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, rs->device) != hipSuccess || cus <= 0)
-            cus = 256;
-        P.n_cus = cus;
-        P.rounds = std::min(rmax, 2);
-        while (P.rounds > 1 &&
-               (int64_t)((R + tile * P.rounds - 1) / (tile * P.rounds)) * P.n_chunks_total < 2 * (int64_t)cus)
-            P.rounds /= 2;
-        // (RCP_GEN_ROUNDS: diagnostics A/B of the rounds per workgroup, 1 / 2 / 4)
-        if (const char* e = std::getenv("RCP_GEN_ROUNDS")) {
-            const int v = std::atoi(e);
-            if (v == 1 || v == 2 || v == 4) P.rounds = std::min(v, rmax);
-        }
-        plan->tile_rows = P.lean == 4 ? tile : (P.lean ? (P.lean_rounds == 2 ? 2 * tile : rcp_tile_rows()) : tile * P.rounds);
-    }
-    plan->grid = (int64_t)((R + plan->tile_rows - 1) / plan->tile_rows) * P.n_chunks_total;
-    if (P.lean == 4) plan->grid = (plan->grid + 7) / 8 * 8;
-    if (plan->lds > 160 * 1024) return fail(RCP_EUNSUPPORTED, "plan needs %zu B of LDS", plan->lds);
-    PLAN_MARK("rest");
-    // cleared before the plan is returned: its executions run on the caller's (non-blocking)
-    // streams, which do not wait for the null stream
-    HIP_TRY(hipMemsetAsync(plan->work.p, 0, plan->work.bytes, nullptr));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    PLAN_MARK("memset");
-    *out = plan.release();
-    return RCP_OK;
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_destroy(rcp_plan* plan) {
-    RCP_TRY
-    if (!plan) return RCP_OK;
-    DeviceGuard g(plan->rs->device);
-    delete plan;
-    return RCP_OK;
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_info_get(const rcp_plan* plan, rcp_plan_info* info) {
-    RCP_TRY
-    if (!plan || !info) return fail(RCP_EINVAL, "NULL argument");
-    info->n_cols = plan->n_cols;
-    info->n_segments = plan->n_seg;
-    info->n_interp_rows = plan->dev.n_interp;
-    info->lds_bytes = (int64_t)plan->lds;
-    info->grid = plan->grid;
-    info->tile_rows = plan->tile_rows;
-    info->chunk_positions = plan->dev.chunk_cap;
-    info->pileup_kernel = plan->dev.lean;
-    info->read_bytes = plan->dev.st ? 4 : 8;
-    info->out_ld = plan->out_ld;
-    info->fold = plan->dev.fold;
-    info->reserved = 0;
-    return RCP_OK;
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_row_lengths(const rcp_plan* plan, int64_t* out_len) {
-    RCP_TRY
-    if (!plan || !out_len) return fail(RCP_EINVAL, "NULL argument");
-    std::memcpy(out_len, plan->row_len.data(), 8 * plan->row_len.size());
-    return RCP_OK;
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_validity(rcp_plan* plan, uint8_t* d_valid, void* hip_stream) {
-    RCP_TRY
-    if (!plan) return fail(RCP_EINVAL, "NULL plan");
-    DeviceGuard g(plan->rs->device);
-    HIP_TRY(g.err);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    begin_exec(plan);
-    RcpPlanDev Q = plan->dev;
-    Q.valid_out = d_valid;
-    HIP_TRY(rcp_launch_locate(&Q, s));
-    Q.heavy_threshold = 0;  // no slices: the heavy launch only zeroes the previous status set
-    HIP_TRY(rcp_launch_heavy(&Q, kHeavyGrid, s));
-    return end_exec(plan, s);
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_execute_stages(rcp_plan* plan, double* d_out, uint8_t* d_valid, int64_t* d_binsum,
-                                       void* hip_stream, int stages) {
-    RCP_TRY
-    if (!plan) return fail(RCP_EINVAL, "NULL plan");
-    if (plan->dev.n_parts == 0) return fail(RCP_EINVAL, "coverage-only plan (created with bins == NULL)");
-    if (!d_out && plan->n_rows && plan->n_cols) return fail(RCP_EINVAL, "NULL output");
-    DeviceGuard g(plan->rs->device);
-    HIP_TRY(g.err);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (stages & RCP_STAGE_LOCATE) {
-        // locate (also clears the previous execution's heavy slots and status words, and writes
-        // the caller's validity vector), heavy slices; a folded plan's pileup kernel does both
-        begin_exec(plan);
-        if (!plan->dev.fold) {
-            RcpPlanDev Q = plan->dev;
-            Q.valid_out = d_valid;
-            HIP_TRY(rcp_launch_locate(&Q, s));
-            HIP_TRY(rcp_launch_heavy(&Q, kHeavyGrid, s));
-        }
-    }
-    // rows with fewer positions than bins (splines of short genes: serial chains) write only their
-    // own cells.  Row-wave plans with the HBM stage pile them in the pileup kernel (interp_stage:
-    // the interpolation kernel, after it, reads their depth from the stage -- no second pileup of
-    // the row); other plans' interpolation reads only locate's outputs and runs on a side stream
-    // beside the pileup, joining the caller's stream after it
-    plan->dev.interp_stage = (plan->dev.lean == 3 && plan->dev.rm32 && !d_binsum) ? 1 : 0;
-    const bool fork = (stages & RCP_STAGE_PILEUP) && (stages & RCP_STAGE_INTERP) && plan->dev.n_interp > 0 &&
-                      !plan->dev.interp_stage && !plan->dev.fold;  // (folded: the pileup kernel locates)
-    if (fork) {
-        if (!plan->side) {
-            HIP_TRY(hipStreamCreateWithFlags(&plan->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&plan->ev_join, hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(plan->ev_fork, s));
-        HIP_TRY(hipStreamWaitEvent(plan->side, plan->ev_fork, 0));
-        HIP_TRY(rcp_launch_interp(&plan->dev, d_out, plan->side));
-        HIP_TRY(hipEventRecord(plan->ev_join, plan->side));
-    }
-    if (stages & RCP_STAGE_PILEUP) {
-        RcpPlanDev Q = plan->dev;
-        if (Q.fold) Q.valid_out = d_valid;
-        HIP_TRY(rcp_launch_pileup(&Q, d_out, d_binsum, 0, s));
-    }
-    // (row-wave plans with the HBM stage interpolate in the pileup kernel: the wave that piled
-    // the row runs its spline)
-    const bool fused = plan->dev.interp_stage && plan->dev.interp_of;
-    if (fork) HIP_TRY(hipStreamWaitEvent(s, plan->ev_join, 0));
-    else if ((stages & RCP_STAGE_INTERP) && !fused) HIP_TRY(rcp_launch_interp(&plan->dev, d_out, s));
-    return end_exec(plan, s);
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_execute(rcp_plan* plan, double* d_out, uint8_t* d_valid, int64_t* d_binsum,
-                                void* hip_stream) {
-    RCP_TRY
-    return rcp_plan_execute_stages(plan, d_out, d_valid, d_binsum, hip_stream, RCP_STAGE_ALL);
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_status(rcp_plan* plan, void* hip_stream) {
-    RCP_TRY
-    if (!plan) return fail(RCP_EINVAL, "NULL plan");
-    DeviceGuard g(plan->rs->device);
-    HIP_TRY(g.err);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    uint32_t st = 0;
-    HIP_TRY(hipMemcpyAsync(&st, plan->dev.status, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (st & RCP_STATUS_WIDTH)
-        return fail(RCP_EUNSUPPORTED, "a per-base part met a row whose slice width differs from the column count");
-    if (st & RCP_STATUS_INTERP) return fail(RCP_EUNSUPPORTED, "internal plan/layout mismatch (status %u)", st);
-    if (st & RCP_STATUS_OVERFLOW) return fail(RCP_EUNSUPPORTED, "bin numerator exceeded 2^32");
-    return RCP_OK;
-    RCP_CATCH
-}
-
-extern "C" int rcp_plan_heavy_rows(rcp_plan* plan, void* hip_stream, int32_t* n_rows) {
-    RCP_TRY
-    if (!plan || !n_rows) return fail(RCP_EINVAL, "NULL argument");
-    DeviceGuard g(plan->rs->device);
-    HIP_TRY(g.err);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    uint32_t n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, plan->dev.status + 1, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *n_rows = (int32_t)std::min<uint32_t>(n, (uint32_t)std::max(plan->dev.heavy_cap, 0));
-    return RCP_OK;
-    RCP_CATCH
-}
 
 extern "C" int rcp_profile(const rcp_readset* rs, const rcp_rows_desc* rows, const rcp_bins_desc* bins, double* out,
                            uint8_t* row_valid) {
@@ -2588,7 +1539,7 @@ int calc_coverage_dev(rcp_plan* plan, const int64_t* d_off, int32_t* d_cov, uint
     P.n_chunks_total = pt.n_chunks;
     P.crange = nullptr;  // sized for the plan's chunks, not these
     P.cw_len = -1;
-    P.lean = 0;  // the general kernel's CSR mode (locate writes every side output)
+    P.lean = RCP_PILEUP_GENERAL;  // the general kernel's CSR mode (locate writes every side output)
     P.fold = 0;
     P.csr_off = d_off;
     P.csr_out = d_cov;
@@ -2618,7 +1569,7 @@ int coverage_starts_dev(rcp_plan* plan, const int64_t* d_off, const int64_t* d_s
     P.n_chunks_total = pt.n_chunks;
     P.crange = nullptr;
     P.cw_len = -1;
-    P.lean = 0;
+    P.lean = RCP_PILEUP_GENERAL;
     P.fold = 0;
     // four rounds of 16 rows per workgroup (C4 coverage pileup 632 -> 601 us vs two, 635 with
     // one; profiles/r04/r4x)

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdint>
+#include <cstdio>
 #include <exception>
 #include <memory>
 #include <mutex>
@@ -18,6 +19,7 @@
 
 #include "../../include/recoup_amd.h"
 #include "rcp_device.h"
+#include "rcp_stage.h"
 
 extern "C" {
 hipError_t rcp_sort_pairs(void* temp, size_t* temp_bytes, const uint64_t* kin, uint64_t* kout, const int32_t* vin,
@@ -104,6 +106,19 @@ extern thread_local std::string g_err;
     catch (...) {                                                                         \
         return fail(RCP_EINVAL, "%s: unexpected C++ exception", __func__);               \
     }
+
+// phase timing of readset builds and plan creation: stderr lines under RCP_TRACE (rcp_stage.h)
+struct PlanTimer {
+    bool on = rcp::trace_on();
+    double t = on ? rcp::trace_ms() : 0.0;
+    void mark(const char* what) {
+        if (!on) return;
+        const double n = rcp::trace_ms();
+        fprintf(stderr, "[plan] %-14s %8.3f ms\n", what, n - t);
+        t = n;
+    }
+};
+#define PLAN_MARK(what) ptimer.mark(what)
 
 // Device buffer with RAII.
 struct DevBuf {
@@ -193,6 +208,9 @@ struct DeviceGuard {
 // RCP_OK, or RCP_ENODEVICE / RCP_EINVAL when `dev` is not a visible device
 int check_device(int dev);
 
+constexpr int kChunkMax = 16384;  // positions of an interpolated slice (block LDS array)
+constexpr int kHeavyGrid = 4096;  // workgroups of the heavy-slice launch
+
 // Run fn(i) for i in [0, n) on one host thread each (one per GPU), collecting the first failure's
 // code and message into the calling thread's rcp_last_error().
 template <class F>
@@ -276,6 +294,14 @@ int cov_copy_parts(const rcp_cov* c, int64_t* run_off, int32_t* values, int32_t*
 enum { kLayMerged = 1, kLayStranded = 2, kLayKeep = 4, kLayIndexOnly = 8, kLayCheckOrder = 16 };
 constexpr int kNotInOrder = 1;
 int readset_build(const rcp_reads_desc* d, hipStream_t s, int layouts, rcp_readset** out);
+// The stranded layout of a readset whose create deferred it, built at its first use (rcp_host.cpp)
+int ensure_stranded(const rcp_readset* rs);
+
+// A plan's executions (rcp_plan.cpp).  begin_exec: alternate the status sets (RcpPlanDev::status /
+// status_prev); the locate kernel clears the previous execution's heavy slots and zeroes its set.
+// end_exec, after an execution's launches on s: the plan's arrays stay allocated until this point
+void begin_exec(rcp_plan* plan);
+int end_exec(rcp_plan* plan, hipStream_t s);
 
 }  // namespace rcpi
 
@@ -373,7 +399,7 @@ struct rcp_readset {
 };
 
 
-// the execution state of a plan (rcp_host.cpp)
+// the execution state of a plan (rcp_plan.cpp)
 struct rcp_plan {
     const rcp_readset* rs = nullptr;
     RcpPlanDev dev{};
@@ -384,6 +410,7 @@ struct rcp_plan {
     size_t lds = 0;
     int64_t grid = 0;
     int32_t tile_rows = 64;  // rows per pileup workgroup (info)
+    bool use_st = false;     // the kernels stream the layout's starts alone (dev.st)
     // device arrays from the pool, released when the plan's last execution has finished (ev_done,
     // or a device synchronisation when it ran on several streams): no hipMalloc / hipFree -- a
     // device-wide synchronisation -- per plan, which would stall the other threads of a pipeline
@@ -399,7 +426,7 @@ struct rcp_plan {
     // stream; made at the first execution that interpolates)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_done = nullptr;  // recorded after every execution (rcp_host.cpp end_exec)
+    hipEvent_t ev_done = nullptr;  // recorded after every execution (rcp_plan.cpp end_exec)
     hipStream_t last = nullptr;    // the executions' stream, when n_streams == 1
     int n_streams = 0;             // 0, 1, 2 = several
     ~rcp_plan() {  // (on the plan's device: rcp_plan_destroy)

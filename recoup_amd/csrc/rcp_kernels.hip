@@ -985,7 +985,7 @@ __device__ __forceinline__ void locate_rows(const RcpPlanDev& P, uint32_t (*xres
     // profiles/r04/r4j/ab.log l1).  Not when the plan interpolates rows: rcp_interp_kernel piles
     // an interpolated row from seg_lo / seg_hi (block_window_depth), and a lean plan may hold
     // such rows (a row shorter than its bins among power-of-two-binned ones)
-    const bool rec_only = fast && P.n_interp == 0 && (P.lean == 1 || P.lean == 2 || P.lean == 4);
+    const bool rec_only = fast && P.n_interp == 0 && (P.lean == RCP_PILEUP_LEAN || P.lean == RCP_PILEUP_LEAN_GEN || P.lean == RCP_PILEUP_BINS);
     if (in_row && q == 0) {
         P.valid[r] = valid ? 1 : 0;
         if (P.valid_out) P.valid_out[r] = valid ? 1 : 0;
@@ -2138,7 +2138,7 @@ __global__ void __launch_bounds__(kPBlock) __attribute__((amdgpu_waves_per_eu(4)
 #include "rcp_splitvector.h"  // splitVector interpolation (also rcp_interp_kernel below)
 
 // ---------------------------------------------------------------------------------
-// Row-wave pileup kernel (mean bins; P.lean == 3): every wave owns whole rows.  For plans
+// Row-wave pileup kernel (mean bins; P.lean == RCP_PILEUP_ROWS): every wave owns whole rows.  For plans
 // whose rows are lists of ranges (coverageRnaRef's c(flank, exons, flank), genebody rows with
 // flanks) the (row tile, column chunk) work items of the general kernel cost a dependent chain
 // of round trips per chunk (pair table -> piece bounds -> first reads) and a workgroup barrier
@@ -2872,7 +2872,7 @@ __device__ __forceinline__ LeanItem lean_item(const RcpPlanDev& P, int code) {
 }
 
 // MAXPER: positions per lane of the widest chunk (16: <= 1023 positions, 8: <= 511).
-// GEN (plan lean == 2): general bins -- any uniform width or R-RNG layouts (splitVector's
+// GEN (plan lean == RCP_PILEUP_LEAN_GEN): general bins -- any uniform width or R-RNG layouts (splitVector's
 // enlarged bins), multi-range rows (exon lists).  Pile waves then stage bin numerators from a
 // cumulative scan (bin-edge differences, as the general kernel) plus a per-row bitmask of the
 // enlarged bins, and store waves divide by the bin width.
@@ -3266,7 +3266,7 @@ rcp_pileup_lean_kernel(RcpPlanDev P, double* __restrict__ out) {
 }
 
 // =================================================================================
-// bin-difference pileup (P.lean == 4): mean profiles whose rows are single ranges cut into
+// bin-difference pileup (P.lean == RCP_PILEUP_BINS): mean profiles whose rows are single ranges cut into
 // uniform bins (every row's slice L = n bs positions: no splitVector layout, no interpolation)
 // of at least kBDMinWidth positions, at most kBDMaxBins bins.  A read adds to BINS, not to
 // positions: its covered row positions [u, v] (clipped) give bins ku = u / bs and kv = v / bs
@@ -3959,12 +3959,12 @@ extern "C" size_t rcp_pileup_lean_lds_bytes(const RcpPlanDev* P) {
     // [pile waves' difference arrays | stage | (general bins) enlarged-bin bits | row metadata
     //  x 2 | item codes x 2]
     return 4 * ((size_t)kLPWaves * P->wave_words + (size_t)kTile * stage_stride(P->stage_cap) +
-                (P->lean == 2 ? (size_t)kTile * 16 : 0)) +
+                (P->lean == RCP_PILEUP_LEAN_GEN ? (size_t)kTile * 16 : 0)) +
            2 * (size_t)kRows * sizeof(LeanMeta) + 16;
 }
 
 static hipError_t launch_pileup_lean(const RcpPlanDev* P, double* out, hipStream_t s) {
-    if (P->lean == 2)
+    if (P->lean == RCP_PILEUP_LEAN_GEN)
         return P->chunk_cap <= 511 ? launch_pileup_lean_r<8, true>(P, out, s) : launch_pileup_lean_r<16, true>(P, out, s);
     return P->chunk_cap <= 511 ? launch_pileup_lean_r<8, false>(P, out, s) : launch_pileup_lean_r<16, false>(P, out, s);
 }
@@ -4024,10 +4024,10 @@ static hipError_t launch_pileup_rows(const RcpPlanDev* P, double* out, int64_t* 
 extern "C" hipError_t rcp_launch_pileup(const RcpPlanDev* P, double* out, int64_t* binsum, int csr,
                                         hipStream_t stream) {
     if (P->n_rows == 0) return hipSuccess;
-    if (!csr && P->lean == 3 && P->stat == 0) return launch_pileup_rows(P, out, binsum, stream);
-    if (!csr && P->lean == 4 && P->stat == 0) return launch_pileup_bins(P, out, binsum, stream);
+    if (!csr && P->lean == RCP_PILEUP_ROWS && P->stat == 0) return launch_pileup_rows(P, out, binsum, stream);
+    if (!csr && P->lean == RCP_PILEUP_BINS && P->stat == 0) return launch_pileup_bins(P, out, binsum, stream);
     const size_t lds = rcp_pileup_lds_bytes(P, csr);
-    if (!csr && (P->lean == 1 || P->lean == 2) && P->stat == 0 && !binsum) return launch_pileup_lean(P, out, stream);
+    if (!csr && (P->lean == RCP_PILEUP_LEAN || P->lean == RCP_PILEUP_LEAN_GEN) && P->stat == 0 && !binsum) return launch_pileup_lean(P, out, stream);
     if (csr) return launch_pileup_t<false, true>(P, out, binsum, lds, stream);
     if (P->stat == 1) return launch_pileup_t<true, false>(P, out, binsum, lds, stream);
     return launch_pileup_t<false, false>(P, out, binsum, lds, stream);

@@ -39,7 +39,7 @@ __device__ __forceinline__ uint32_t ub_start(const int2* __restrict__ se, uint32
 // merged: every strand lives in slot 0; else slot k holds strand k and the range searches the
 // slots findOverlaps' strand compatibility allows ('*' matches everything).  A range the locate
 // kernel never searches (absent chromosome, end < start) gets [0, 0).  The range searched is
-// [max(start, 1), end]: R drops index 0 (rcp_host.cpp build_rows).
+// [max(start, 1), end]: R drops index 0 (rcp_plan.cpp build_rows).
 __global__ void __launch_bounds__(kB) rcp_seg_bounds_kernel(int64_t n_seg, const int32_t* __restrict__ chrom,
                                                             const int32_t* __restrict__ start,
                                                             const int32_t* __restrict__ end,
