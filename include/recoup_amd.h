@@ -405,6 +405,59 @@ RCP_API int rcp_cov_info(const rcp_cov* c, int32_t* n_rows, int64_t* n_runs);
 RCP_API int rcp_cov_copy(const rcp_cov* c, int64_t* run_off, int32_t* values, int32_t* lengths, uint8_t* valid);
 RCP_API int rcp_cov_free(rcp_cov* c);
 
+/* ------------------------------------------------------------------ summaries of kept matrices */
+/* What every consumer of `$profile` reduces the matrix to again (R/plot.R), computed where the
+ * matrix is: S sample matrices as rcp_plan_execute wrote them, column c of sample s at
+ * d_mat[s] + c * ld, rows 0 .. n_rows-1 of each column (rows n_rows .. ld-1 are padding and are
+ * never read).  d_mat is a host array of device pointers; a caller selects a column range by
+ * offsetting them (a recoupProfiles matrix holds the heatmap's columns after the profile's).
+ * log2p1 applies x -> log2(x + 1) to every element first (plotParams$signalScale = "log2",
+ * plot.R:953-956, :481-486).  All three calls only enqueue work on hip_stream (scratch from the
+ * library's pool, no host synchronisation); outputs are device arrays.  Arguments are checked
+ * before the device is touched.  n_rows = 0 or n_cols = 0 is legal.
+ *
+ * Numerics: no floating-point atomics; every reduction's shape depends on (n_rows, n_cols) alone,
+ * so results are bit-identical from run to run, on any stream.  sd is sqrt(sum of squared
+ * deviations about the mean / (n - 1)), merged from partial (n, mean, M2) triples (Chan et al.),
+ * never sum(x^2) - n * mean^2. */
+typedef struct {
+    int64_t n_rows, n_cols, ld;   /* ld >= n_rows */
+    int32_t n_samples;            /* >= 1 */
+    int32_t log2p1;               /* 1: log2(x + 1) first */
+    const double* const* d_mat;   /* [n_samples] device pointers (host array) */
+} rcp_matrix_desc;
+#define RCP_SUMMARY_MAX_GROUPS 64
+
+/* Column statistics: replaces apply(profile, 2, mean) / apply(profile, 2, sd) of calcPlotProfiles
+ * (R/plot.R:976-988) and, with group ids, of calcDesignPlotProfiles over the rows of each design
+ * level (R/plot.R:1019-1031).  d_group: device int32 [n_rows], ids in [0, n_groups); any other
+ * value (e.g. -1) leaves the row out; NULL: all rows are group 0 (n_groups ignored).  n_groups >
+ * RCP_SUMMARY_MAX_GROUPS: RCP_EUNSUPPORTED.  Outputs [n_samples][n_groups][n_cols], any may be
+ * NULL: the mean, the sd (n - 1 divisor) and the count of rows.  As in R, n = 0 gives a NaN mean
+ * and sd (mean(numeric(0))), n = 1 a NaN sd. */
+RCP_API int rcp_summary_cols(const rcp_matrix_desc* m, const int32_t* d_group, int32_t n_groups, double* d_mean,
+                             double* d_sd, int64_t* d_count, void* hip_stream);
+/* Row statistics over the n_cols columns: replaces apply(profile, 1, sum | max | mean) of
+ * orderProfiles (R/plot.R:1082-1177) and apply(profile, 1, mean | sd) of calcPlotProfiles(sdim = 1)
+ * as recoupCorrelation uses it.  Outputs [n_samples][n_rows], any may be NULL. */
+RCP_API int rcp_summary_rows(const rcp_matrix_desc* m, double* d_sum, double* d_max, double* d_mean, double* d_sd,
+                             void* hip_stream);
+/* Row order: replaces the key and sort(..., index.return = TRUE) of orderProfiles
+ * (R/plot.R:1068-1183) and, with group ids, orderProfilesByDesign (R/plot.R:1186-1330).  The key
+ * of a row is its sum / max / mean (what) in sample ref_sample, or for ref_sample = -1 the sum of
+ * the samples' sums, the max of their maxes, the mean of their means (samples added in list
+ * order).  d_order (device int32 [n_rows]) receives the 0-based rows in ascending key order, or
+ * descending when decreasing != 0; equal keys (-0.0 equals 0.0, as R compares them) keep row
+ * order in both directions.  That is the order of R's radix method, which sort(index.return =
+ * TRUE) uses for vectors shorter than 2^31; R is not available to this project's tests, so this
+ * rests on R's documentation of sort / order.  With d_group (as for rcp_summary_cols): groups in
+ * ascending id, each group's rows ordered among themselves, then the rows no group holds in row
+ * order.  d_key (device [n_rows], may be NULL) receives every row's key. */
+enum { RCP_KEY_SUM = 0, RCP_KEY_MAX = 1, RCP_KEY_AVG = 2 };
+RCP_API int rcp_order_rows(const rcp_matrix_desc* m, int32_t what, int32_t ref_sample, int32_t decreasing,
+                           const int32_t* d_group, int32_t n_groups, int32_t* d_order, double* d_key,
+                           void* hip_stream);
+
 /* ------------------------------------------------------------------ BAM ingest */
 /* readBam (R/ranges.R:111-146) on the host: BGZF blocks inflated by n_threads threads, mapped
  * alignments (readGAlignments) turned into 1-based ranges on their reference and strand:

@@ -11,5 +11,6 @@ from .granges import (GRanges, GRangesList, flank, getFlankingRanges, getRegiona
                       promoters, resize)
 from .api import (CoverageList, DeviceCoverage, RMatrix, Rle, baseCoverageMatrix, binCoverageMatrix,  # noqa: F401
                   calcCoverage, calcLinearFactors, coverageRef, coverageRnaRef, normalizeLinear, profileMatrix,
-                  RRng, preprocessRanges, readBam, recoupProfiles)
+                  RRng, preprocessRanges, readBam, recoupProfiles, calcPlotProfiles, calcDesignPlotProfiles,
+                  designGroups, orderProfiles, orderProfilesByDesign, parseOrderWhat)
 from ._lib import RcpError, SemanticError, UnsupportedError  # noqa: F401

@@ -79,6 +79,11 @@ class PlanOpts(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 2)]
 
 
+class MatrixDesc(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int64), ("n_cols", ctypes.c_int64), ("ld", ctypes.c_int64),
+                ("n_samples", ctypes.c_int32), ("log2p1", ctypes.c_int32), ("d_mat", ctypes.POINTER(_vp))]
+
+
 # every symbol include/recoup_amd.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("rcp_version", ctypes.c_char_p, []),
@@ -126,6 +131,10 @@ SIGNATURES = [
     ("rcp_cov_copy", ctypes.c_int, [_vp, _i64p, _i32p, _i32p, _u8p]),
     ("rcp_cov_free", ctypes.c_int, [_vp]),
     ("rcp_profile_cov", ctypes.c_int, [_vp, ctypes.POINTER(BinsDesc), _dp, _u8p]),
+    ("rcp_summary_cols", ctypes.c_int, [ctypes.POINTER(MatrixDesc), _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    ("rcp_summary_rows", ctypes.c_int, [ctypes.POINTER(MatrixDesc), _vp, _vp, _vp, _vp, _vp]),
+    ("rcp_order_rows", ctypes.c_int, [ctypes.POINTER(MatrixDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
+                                      ctypes.c_int32, _vp, _vp, _vp]),
     ("rcp_bam_read", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                     ctypes.POINTER(_vp)]),
     ("rcp_bam_info", ctypes.c_int, [_vp, _i64p, _i32p, _i64p]),

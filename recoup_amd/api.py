@@ -626,3 +626,259 @@ def preprocessRanges(input, preprocessParams=None, bamParams=None, rc=None):
             idx = rng.sample_sorted(n, size) - 1
             s["ranges"] = s["ranges"][idx]
     return input
+
+
+# ------------------------------------------------------------------------------ summaries
+# What the plotting layer reduces ``$profile`` to (R/plot.R), computed on the matrix that
+# profileMatrix / recoupProfiles(keep_on_device=True) left in HBM as ``sample["profile_device"]``:
+# only the curves (n_cols numbers) and orders (n_rows integers) cross PCIe.
+#
+#   calcPlotProfiles(input, opts, sdim)                R/plot.R:949-990
+#   calcDesignPlotProfiles(input, design, opts, sdim)  R/plot.R:992-1033
+#   orderProfiles(input, opts)                         R/plot.R:1035-1184
+#   orderProfilesByDesign(input, design, opts)         R/plot.R:1186-1350
+#
+# Not on this path (UnsupportedError): sumStat = "median" with mad bands, plotParams$smooth
+# (smooth.spline + ssCI work on the n_cols-long curve returned here and stay with the caller),
+# "hc" (hierarchical clustering) orders, kmeansDesign.
+_KEY = {"sum": 0, "max": 1, "avg": 2}
+
+
+def parseOrderWhat(what):
+    """orderBy$what as R/plot.R:1044-1066 reads it: ``(stat, ref)`` with stat "sum" / "max" /
+    "avg" and ref 0 = all samples or the 1-based reference sample; ``(None, 1)`` for a value
+    that names no statistic ("none": the identity order).  The last character decides the
+    reference: "a" = all, a digit = that sample, anything else warns and takes the first."""
+    import warnings
+    what = str(_first(what, "none"))
+    if what.startswith("hc"):
+        raise _lib.UnsupportedError(-4, f"orderBy$what = {what!r}: hierarchical clustering (hc) orders are not "
+                                        "on the device path")
+    m = re.match(r"^(sum|max|avg)", what)
+    if m is None:
+        return None, 1
+    rh = what[-1]
+    if rh == "a":
+        return m.group(1), 0
+    if rh.isdigit():
+        return m.group(1), int(rh)
+    warnings.warn("Reference profile for heatmap ordering not recognized! Using the 1st...")
+    return m.group(1), 1
+
+
+def _plot_params(opts):
+    pp = (opts or {}).get("plotParams") or {}
+    stat = str(_first(pp.get("sumStat"), "mean")).lower()
+    if stat == "median":
+        raise _lib.UnsupportedError(-4, 'plotParams$sumStat = "median" (median curves with mad bands) needs a '
+                                        "selection kernel this build does not have; there is no CPU fallback")
+    if stat != "mean":
+        raise _lib.SemanticError(-5, f"plotParams$sumStat = {stat!r} is neither mean nor median")
+    if pp.get("smooth"):
+        raise _lib.UnsupportedError(-4, "plotParams$smooth (smooth.spline + ssCI) works on the curve this function "
+                                        "returns and stays with the caller: call with smooth = False")
+    scale = str(_first(pp.get("signalScale"), "natural"))
+    if scale not in ("natural", "log2"):
+        raise _lib.SemanticError(-5, f"plotParams$signalScale = {scale!r} is neither natural nor log2")
+    return scale == "log2"
+
+
+def _kept_matrix(sample):
+    """(tensor, n_rows, n_cols, ld) of a sample's kept matrix; n_cols: the profile's own columns
+    (a recoupProfiles matrix holds the heatmap's after them)."""
+    t = sample.get("profile_device")
+    if t is None:
+        raise ValueError(f"sample {sample.get('id')!r} has no profile_device: run profileMatrix / recoupProfiles "
+                         "with keep_on_device=True")
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 2):
+        raise TypeError("profile_device must be a 2-d float64 device tensor (columns x rows)")
+    n_total, n_rows = int(t.shape[0]), int(t.shape[1])
+    if n_rows > 1 and t.stride(1) != 1:
+        raise TypeError("profile_device must hold each column contiguously")
+    ld = int(t.stride(0)) if n_total > 1 else max(n_rows, 1)
+    prof = sample.get("profile")
+    n_cols = n_total if prof is None else min(int(prof.shape[1]), n_total)
+    return t, n_rows, n_cols, max(ld, n_rows)
+
+
+def _desc(tensors, n_rows, n_cols, ld, log2p1):
+    import ctypes
+    arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    d = _lib.MatrixDesc(n_rows, n_cols, ld, len(tensors), int(bool(log2p1)), arr)
+    d._keep = (arr, tensors)
+    return d
+
+
+def designGroups(design, n_rows):
+    """Rows -> groups as ``split(1:nrow(design), design, drop=TRUE)`` forms them: ``design`` is a
+    per-row array of level codes, or a list of such arrays whose existing combinations are the
+    groups (first factor varying fastest, names joined with "."); None / NaN leaves a row out.
+    Returns (int32 group id per row, -1 = left out; the groups' names)."""
+    factors = design if isinstance(design, (list, tuple)) and len(design) and np.ndim(design[0]) == 1 else [design]
+    code = np.zeros(n_rows, np.int64)
+    out = np.zeros(n_rows, bool)
+    mult = 1
+    levels = []
+    for f in factors:
+        f = np.asarray(f)
+        if f.shape != (n_rows,):
+            raise _lib.SemanticError(-5, f"a design factor has shape {f.shape}, the profile {n_rows} rows")
+        na = np.array([x is None or (isinstance(x, float) and x != x) for x in f.tolist()], bool)
+        lv = sorted(set(np.asarray(f[~na]).tolist()))
+        idx = {v: k for k, v in enumerate(lv)}
+        code += mult * np.array([0 if m else idx[v] for v, m in zip(f.tolist(), na)], np.int64).reshape(n_rows)
+        out |= na
+        mult *= max(len(lv), 1)
+        levels.append(lv)
+    present = np.unique(code[~out])
+    gid = np.full(n_rows, -1, np.int32)
+    gid[~out] = np.searchsorted(present, code[~out]).astype(np.int32)
+    names = []
+    for c in present.tolist():
+        parts = []
+        for lv in levels:
+            parts.append(str(lv[c % max(len(lv), 1)]))
+            c //= max(len(lv), 1)
+        names.append(".".join(parts))
+    return gid, names
+
+
+def _col_stats(sample, log2p1, gid=None, n_groups=1):
+    t, n_rows, n_cols, ld = _kept_matrix(sample)
+    dev = t.device
+    G = n_groups if gid is not None else 1
+    mean = torch.empty(max(G * n_cols, 1), dtype=torch.float64, device=dev)
+    sd = torch.empty_like(mean)
+    d_gid = None if gid is None else torch.from_numpy(gid).to(dev)
+    d = _desc([t], n_rows, n_cols, ld, log2p1)
+    import ctypes
+    _lib.check(_lib.lib().rcp_summary_cols(ctypes.byref(d), _lib.ptr(d_gid), G, _lib.ptr(mean), _lib.ptr(sd), None,
+                                           _lib.stream_handle(dev)))
+    return (mean[:G * n_cols].cpu().numpy().reshape(G, n_cols), sd[:G * n_cols].cpu().numpy().reshape(G, n_cols))
+
+
+def _row_stats(sample, log2p1):
+    t, n_rows, n_cols, ld = _kept_matrix(sample)
+    mean = torch.empty(max(n_rows, 1), dtype=torch.float64, device=t.device)
+    sd = torch.empty_like(mean)
+    d = _desc([t], n_rows, n_cols, ld, log2p1)
+    import ctypes
+    _lib.check(_lib.lib().rcp_summary_rows(ctypes.byref(d), None, None, _lib.ptr(mean), _lib.ptr(sd),
+                                           _lib.stream_handle(t.device)))
+    return mean[:n_rows].cpu().numpy(), sd[:n_rows].cpu().numpy()
+
+
+def _band(m, v):
+    return {"profile": m, "upper": m + v, "lower": m - v}  # plot.R:982-986
+
+
+def calcPlotProfiles(input, opts, sdim=2, rc=None):
+    """R/plot.R:949-990 without smoothing: per sample ``{"profile", "upper", "lower"}`` -- the mean
+    over dimension ``sdim`` (2: one value per column, the average curve; 1: one per row, as
+    recoupCorrelation asks) of the kept matrix, after log2(x + 1) when plotParams$signalScale is
+    "log2", and mean +- sd.  Reads ``sample["profile_device"]`` only; a list in sample order."""
+    log2p1 = _plot_params(opts)
+    sdim = int(_first(sdim, 2))
+    if sdim not in (1, 2):
+        raise _lib.SemanticError(-5, "sdim must be 1 or 2")
+    out = []
+    for s in input:
+        if sdim == 2:
+            m, v = _col_stats(s, log2p1)
+            out.append(_band(m[0], v[0]))
+        else:
+            out.append(_band(*_row_stats(s, log2p1)))
+    return out
+
+
+def calcDesignPlotProfiles(input, design, opts, sdim=2, rc=None):
+    """R/plot.R:992-1033 over the sub-matrices recoupProfile cuts by design
+    (``x$profile[splitter[[level]], ]``): per sample a dict ``{level name: {"profile", "upper",
+    "lower"}}``; every level of a sample comes from one launch sequence.  ``design``: see
+    designGroups."""
+    log2p1 = _plot_params(opts)
+    sdim = int(_first(sdim, 2))
+    if sdim not in (1, 2):
+        raise _lib.SemanticError(-5, "sdim must be 1 or 2")
+    out = []
+    for s in input:
+        gid, names = designGroups(design, _kept_matrix(s)[1])
+        if sdim == 2:
+            m, v = _col_stats(s, log2p1, gid, max(len(names), 1))
+            out.append({nm: _band(m[k], v[k]) for k, nm in enumerate(names)})
+        else:
+            m, v = _row_stats(s, log2p1)
+            out.append({nm: _band(m[gid == k], v[gid == k]) for k, nm in enumerate(names)})
+    return out
+
+
+def _host_sort(x, decreasing):
+    """sort(x, decreasing, index.return=TRUE) on the host: equal values keep their order in both
+    directions (R's radix method)."""
+    x = np.asarray(x, dtype=np.float64)
+    ix = np.argsort(-x if decreasing else x, kind="stable")
+    return {"x": x[ix], "ix": ix.astype(np.int64)}
+
+
+def _order_opts(opts):
+    ob = (opts or {}).get("orderBy") or {}
+    return ob, str(_first(ob.get("order"), "descending")) == "descending"
+
+
+def _device_order(input, stat, ref, decreasing, gid=None, n_groups=0):
+    import ctypes
+    mats = [_kept_matrix(s) for s in input]
+    if ref > len(mats):
+        raise _lib.SemanticError(-5, f"orderBy$what names sample {ref} of {len(mats)}: subscript out of bounds")
+    t0, n_rows, n_cols, ld = mats[0]
+    if any(m[1:] != (n_rows, n_cols, ld) for m in mats) or any(m[0].device != t0.device for m in mats):
+        if ref == 0:
+            raise _lib.SemanticError(-5, "the samples' kept matrices differ in shape, stride or device")
+        t0, n_rows, n_cols, ld = mats[ref - 1]
+        mats, ref = [mats[ref - 1]], 1
+    order = torch.empty(max(n_rows, 1), dtype=torch.int32, device=t0.device)
+    key = torch.empty(max(n_rows, 1), dtype=torch.float64, device=t0.device)
+    d_gid = None if gid is None else torch.from_numpy(gid).to(t0.device)
+    d = _desc([m[0] for m in mats], n_rows, n_cols, ld, False)
+    _lib.check(_lib.lib().rcp_order_rows(ctypes.byref(d), _KEY[stat], ref - 1, int(decreasing), _lib.ptr(d_gid),
+                                         n_groups, _lib.ptr(order), _lib.ptr(key), _lib.stream_handle(t0.device)))
+    return order[:n_rows].cpu().numpy().astype(np.int64), key[:n_rows].cpu().numpy()
+
+
+def orderProfiles(input, opts, rc=None):
+    """R/plot.R:1035-1184: ``{"x", "ix"}`` as ``sort(theVal, decreasing, index.return=TRUE)``
+    returns them -- ``ix`` the rows in heatmap order, **0-based** (R's are 1-based), ``x`` their
+    keys in that order.  orderBy$custom is sorted on the host, as the reference does; "none"
+    gives the identity order (``ix`` alone, as in R); keys come from ``profile_device``."""
+    ob, decreasing = _order_opts(opts)
+    if ob.get("custom") is not None:
+        return _host_sort(ob["custom"], decreasing)
+    stat, ref = parseOrderWhat(ob.get("what", "none"))
+    if stat is None:
+        return {"ix": np.arange(_kept_matrix(input[0])[1], dtype=np.int64)}
+    ix, key = _device_order(input, stat, ref, decreasing)
+    return {"x": key[ix], "ix": ix}
+
+
+def orderProfilesByDesign(input, design, opts, rc=None):
+    """R/plot.R:1186-1350: the rows of each design group (designGroups; groups in level order)
+    ordered among themselves, concatenated -- ``unlist(sorter)`` -- as ``{"x", "ix"}`` with
+    **0-based** ``ix``; rows the design leaves out (NA) are dropped, as split() drops them."""
+    ob, decreasing = _order_opts(opts)
+    n_rows = _kept_matrix(input[0])[1] if ob.get("custom") is None else len(ob["custom"])
+    gid, names = designGroups(design, n_rows)
+    if ob.get("custom") is not None:
+        x = np.asarray(ob["custom"], dtype=np.float64)
+        parts = []
+        for k in range(len(names)):
+            rows = np.flatnonzero(gid == k)
+            parts.append(rows[_host_sort(x[rows], decreasing)["ix"]])
+        ix = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        return {"x": x[ix], "ix": ix.astype(np.int64)}
+    stat, ref = parseOrderWhat(ob.get("what", "none"))
+    if stat is None:
+        ix = np.argsort(np.where(gid < 0, len(names), gid), kind="stable")[:int((gid >= 0).sum())]
+        return {"ix": ix.astype(np.int64)}
+    ix, key = _device_order(input, stat, ref, decreasing, gid, max(len(names), 1))
+    ix = ix[:int((gid >= 0).sum())]
+    return {"x": key[ix], "ix": ix}
