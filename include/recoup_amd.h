@@ -458,6 +458,43 @@ RCP_API int rcp_order_rows(const rcp_matrix_desc* m, int32_t what, int32_t ref_s
                            const int32_t* d_group, int32_t n_groups, int32_t* d_order, double* d_key,
                            void* hip_stream);
 
+/* Exact quantiles of kept matrices: replaces quantile(input[[n]]$profile, q) of recoupHeatmap's
+ * colour limits (R/plot.R:510-545) and apply(profile, 2, median) / apply(profile, 2, mad) of
+ * calcPlotProfiles with sumStat = "median" (R/plot.R:976-988), after the optional log2(x + 1).
+ * A segment is the whole n_rows x n_cols matrix of one sample (RCP_QUANTILE_MATRIX) or one
+ * column of it (RCP_QUANTILE_COLS); padding rows are never read.  The formulas are R's
+ * quantile.default (type 7), median.default and mad restated from R's source as remembered; R is
+ * not available to this project's tests.  With x_(1) <= ... <= x_(n) the segment's elements
+ * (-0.0 equals 0.0; a selected zero is returned as +0.0):
+ *   index = 1 + (n - 1) * p in fp64, lo = floor(index), hi = ceil(index), h = index - lo
+ *   q = x_(lo)                             if index == lo or x_(hi) == x_(lo)
+ *   q = (1 - h) * x_(lo) + h * x_(hi)      otherwise; both products and the sum round separately
+ *                                          (no FMA), as R on x86-64 computes them
+ * (the x_(hi) == x_(lo) guard keeps Inf - Inf out of a tie of infinities).  The median is the
+ * quantile at 0.5 -- for even n 0.5 * a + 0.5 * b, which cannot overflow; R's mean(c(a, b)) goes
+ * through long double and may differ by one ulp in rare double-rounding cases (known, unverified
+ * difference).  mad = 1.4826 * median(|x - median(x)|), one rounding per operation.  n = 0
+ * gives NaN (R's NA).  A segment that holds any NaN gives NaN for every result of it: R's median
+ * returns NA there, R's quantile stops with an error (a difference).  Selection is exact (a radix
+ * selection over order-preserving 64-bit keys with integer atomics only): results are
+ * bit-identical from run to run, on any stream, and the numerics paragraph above holds word for
+ * word.  Segment counters are 32-bit: a segment of 2^32 or more elements is RCP_EUNSUPPORTED.
+ * Both calls only enqueue work on hip_stream with pool scratch bounded by histograms and
+ * per-segment state (never a copy of the matrix); arguments are checked before the device is
+ * touched; n_rows = 0 or n_cols = 0 is legal (with n_cols = 0 in column scope nothing is written). */
+#define RCP_QUANTILE_MAX_PROBS 8
+enum { RCP_QUANTILE_MATRIX = 0, RCP_QUANTILE_COLS = 1 };
+/* d_q: device [n_samples][n_segments][n_probs]; n_segments = 1 or n_cols.  probs: host array of
+ * n_probs probabilities in [0, 1] (NaN or outside: RCP_EINVAL, where R stops too);
+ * n_probs > RCP_QUANTILE_MAX_PROBS: RCP_EUNSUPPORTED. */
+RCP_API int rcp_summary_quantiles(const rcp_matrix_desc* m, int32_t scope, const double* probs, int32_t n_probs,
+                                  double* d_q, void* hip_stream);
+/* per column: d_median, d_mad device [n_samples][n_cols], either may be NULL (not both) */
+RCP_API int rcp_summary_median_mad(const rcp_matrix_desc* m, double* d_median, double* d_mad, void* hip_stream);
+/* The rank arithmetic above on the host (no device): lo, hi (1-based) and h of probability p over
+ * n elements; n = 0 gives lo = hi = 0.  RCP_EINVAL for n < 0, a NULL output or p NaN / outside [0, 1]. */
+RCP_API int rcp_quantile_ranks(int64_t n, double p, int64_t* lo, int64_t* hi, double* h);
+
 /* ------------------------------------------------------------------ BAM ingest */
 /* readBam (R/ranges.R:111-146) on the host: BGZF blocks inflated by n_threads threads, mapped
  * alignments (readGAlignments) turned into 1-based ranges on their reference and strand:

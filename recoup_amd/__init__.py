@@ -12,5 +12,6 @@ from .granges import (GRanges, GRangesList, flank, getFlankingRanges, getRegiona
 from .api import (CoverageList, DeviceCoverage, RMatrix, Rle, baseCoverageMatrix, binCoverageMatrix,  # noqa: F401
                   calcCoverage, calcLinearFactors, coverageRef, coverageRnaRef, normalizeLinear, profileMatrix,
                   RRng, preprocessRanges, readBam, recoupProfiles, calcPlotProfiles, calcDesignPlotProfiles,
-                  designGroups, orderProfiles, orderProfilesByDesign, parseOrderWhat)
+                  designGroups, orderProfiles, orderProfilesByDesign, parseOrderWhat, profileQuantiles,
+                  heatmapColorLimits, calcMedianPlotProfiles, walkHeatmapLadder, HEATMAP_LADDER)
 from ._lib import RcpError, SemanticError, UnsupportedError  # noqa: F401

@@ -135,6 +135,9 @@ SIGNATURES = [
     ("rcp_summary_rows", ctypes.c_int, [ctypes.POINTER(MatrixDesc), _vp, _vp, _vp, _vp, _vp]),
     ("rcp_order_rows", ctypes.c_int, [ctypes.POINTER(MatrixDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
                                       ctypes.c_int32, _vp, _vp, _vp]),
+    ("rcp_summary_quantiles", ctypes.c_int, [ctypes.POINTER(MatrixDesc), ctypes.c_int32, _dp, ctypes.c_int32, _vp, _vp]),
+    ("rcp_summary_median_mad", ctypes.c_int, [ctypes.POINTER(MatrixDesc), _vp, _vp, _vp]),
+    ("rcp_quantile_ranks", ctypes.c_int, [ctypes.c_int64, ctypes.c_double, _i64p, _i64p, _dp]),
     ("rcp_bam_read", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                     ctypes.POINTER(_vp)]),
     ("rcp_bam_info", ctypes.c_int, [_vp, _i64p, _i32p, _i64p]),

@@ -638,7 +638,8 @@ def preprocessRanges(input, preprocessParams=None, bamParams=None, rc=None):
 #   orderProfiles(input, opts)                         R/plot.R:1035-1184
 #   orderProfilesByDesign(input, design, opts)         R/plot.R:1186-1350
 #
-# Not on this path (UnsupportedError): sumStat = "median" with mad bands, plotParams$smooth
+# Not on this path (UnsupportedError): sumStat = "median" in these functions (the median curve with
+# mad bands is calcMedianPlotProfiles, further down), plotParams$smooth
 # (smooth.spline + ssCI work on the n_cols-long curve returned here and stay with the caller),
 # "hc" (hierarchical clustering) orders, kmeansDesign.
 _KEY = {"sum": 0, "max": 1, "avg": 2}
@@ -882,3 +883,128 @@ def orderProfilesByDesign(input, design, opts, rc=None):
     ix, key = _device_order(input, stat, ref, decreasing, gid, max(len(names), 1))
     ix = ix[:int((gid >= 0).sum())]
     return {"x": key[ix], "ix": ix}
+
+
+# ------------------------------------------------------------------------------ quantiles of kept matrices
+# The order statistics of `$profile` (R/plot.R): the heatmap colour limits quantile(profile, q) of
+# recoupHeatmap (:510-545) and the median curves with mad bands of calcPlotProfiles (:976-988),
+# selected exactly where the matrix is (rcp_summary_quantiles / rcp_summary_median_mad): seven
+# scalars or a curve of n_cols numbers cross PCIe, never the matrix.
+HEATMAP_LADDER = (0.95, 0.96, 0.97, 0.98, 0.99, 0.995, 0.999)  # plot.R:515: qs
+_SCOPE = {"matrix": 0, "column": 1}
+
+
+def _kept_columns(sample, which):
+    """(tensor, n_rows, first column, n_cols, ld) of the profile's own columns or of the heatmap
+    columns a fused recoupProfiles pass kept after them."""
+    if which not in ("profile", "heatmap"):
+        raise ValueError(f"which = {which!r} is neither 'profile' nor 'heatmap'")
+    t, prof = sample.get("profile_device"), sample.get("profile")
+    if which == "heatmap" and isinstance(t, torch.Tensor) and t.dim() == 2:  # (a shape question: asked first)
+        if prof is None or int(t.shape[0]) <= int(prof.shape[1]):
+            raise ValueError(f"sample {sample.get('id')!r}: profile_device holds no heatmap columns (they follow "
+                             "the profile's only after a fused recoupProfiles pass)")
+    t, n_rows, n_cols, ld = _kept_matrix(sample)
+    if which == "profile":
+        return t, n_rows, 0, n_cols, ld
+    return t, n_rows, n_cols, int(t.shape[0]) - n_cols, ld
+
+
+def _col_desc(t, n_rows, col0, n_cols, ld, log2p1):
+    import ctypes
+    arr = (ctypes.c_void_p * 1)(t.data_ptr() + 8 * col0 * ld)
+    d = _lib.MatrixDesc(n_rows, n_cols, ld, 1, int(bool(log2p1)), arr)
+    d._keep = (arr, t)
+    return d
+
+
+def _scale_log2(scale):
+    scale = str(_first(scale, "natural"))
+    if scale not in ("natural", "log2"):
+        raise _lib.SemanticError(-5, f"signalScale = {scale!r} is neither natural nor log2")
+    return scale == "log2"
+
+
+def profileQuantiles(input, probs, by="matrix", scale="natural", which="profile"):
+    """Exact type-7 quantiles (R's ``quantile(x, probs)``) of every sample's kept matrix, after
+    log2(x + 1) when ``scale`` is "log2": per sample an array of shape ``(n_probs,)`` over the
+    whole matrix (``by="matrix"``) or ``(n_cols, n_probs)`` per column (``by="column"``).  Up to
+    8 probabilities per call.  ``which="heatmap"`` takes the heatmap columns a fused recoupProfiles
+    pass kept after the profile's.  A matrix or column that holds a NaN gives NaN (R's quantile
+    stops there).  Reads ``sample["profile_device"]`` only."""
+    import ctypes
+    if by not in _SCOPE:
+        raise ValueError(f"by = {by!r} is neither 'matrix' nor 'column'")
+    log2p1 = _scale_log2(scale)
+    p = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+    out = []
+    for s in input:
+        t, n_rows, col0, n_cols, ld = _kept_columns(s, which)
+        n_seg = n_cols if by == "column" else 1
+        q = torch.empty(max(n_seg * len(p), 1), dtype=torch.float64, device=t.device)
+        d = _col_desc(t, n_rows, col0, n_cols, ld, log2p1)
+        _lib.check(_lib.lib().rcp_summary_quantiles(ctypes.byref(d), _SCOPE[by], _lib.cptr(p, _lib._dp), len(p),
+                                                    _lib.ptr(q), _lib.stream_handle(t.device)))
+        q = q[:n_seg * len(p)].cpu().numpy()
+        out.append(q.reshape(n_seg, len(p)) if by == "column" else q)
+    return out
+
+
+def walkHeatmapLadder(qvals):
+    """plot.R:515-523 with heatmapScale = "each": ``qvals`` are the quantiles at HEATMAP_LADDER;
+    the limit is the first that is not 0.  When all seven are 0 the reference indexes qs[8], an
+    NA probability, and quantile() stops: SemanticError."""
+    for v in np.asarray(qvals, dtype=np.float64).tolist():
+        if v != 0:
+            return v
+    raise _lib.SemanticError(-5, "plot.R:520: quantile(input[[n]]$profile, qs[8]): missing values and NaN's not "
+                                 "allowed if 'na.rm' is FALSE (all seven ladder quantiles of the profile are 0)")
+
+
+def heatmapColorLimits(input, opts, which="profile"):
+    """The colour limits of recoupHeatmap (R/plot.R:510-545): ``{"sup": per-sample array,
+    "limits": [(0.0, heatmapFactor * sup), ...]}``.  plotParams$heatmapScale = "each": per sample
+    the first non-zero of the quantiles at 0.95 .. 0.999 (one device call with the seven
+    probabilities; the ladder is walked on the host); "common": the maximum of the samples' 0.95
+    quantiles for every sample.  Quantiles are taken after log2(x + 1) when plotParams$signalScale
+    is "log2" (plot.R:481-486)."""
+    pp = (opts or {}).get("plotParams") or {}
+    hs = str(_first(pp.get("heatmapScale"), "common"))
+    if hs not in ("each", "common"):
+        raise _lib.SemanticError(-5, f"plotParams$heatmapScale = {hs!r} is neither each nor common")
+    factor = float(_first(pp.get("heatmapFactor"), 1.0))
+    scale = _first(pp.get("signalScale"), "natural")
+    _scale_log2(scale)
+    if hs == "each":
+        qs = profileQuantiles(input, HEATMAP_LADDER, by="matrix", scale=scale, which=which)
+        sup = np.array([walkHeatmapLadder(q) for q in qs], dtype=np.float64)
+    else:
+        qs = profileQuantiles(input, [0.95], by="matrix", scale=scale, which=which)
+        sup = np.full(len(qs), max(float(q[0]) for q in qs) if qs else np.nan, dtype=np.float64)
+    return {"sup": sup, "limits": [(0.0, factor * float(v)) for v in sup]}
+
+
+def calcMedianPlotProfiles(input, opts, sdim=2):
+    """R/plot.R:976-988 with sumStat = "median", without smoothing: per sample ``{"profile": median,
+    "upper": median + mad, "lower": median - mad}`` per column of the kept matrix, after
+    log2(x + 1) when plotParams$signalScale is "log2".  median is the type-7 quantile at 0.5, mad
+    = 1.4826 * median(|x - median|), both selected exactly on the device.  Row medians (sdim = 1)
+    and plotParams$smooth are not on this path."""
+    pp = (opts or {}).get("plotParams") or {}
+    if int(_first(sdim, 2)) != 2:
+        raise _lib.UnsupportedError(-4, "calcMedianPlotProfiles: row medians (sdim = 1) are not on the device path")
+    if pp.get("smooth"):
+        raise _lib.UnsupportedError(-4, "plotParams$smooth (smooth.spline + ssCI) works on the curve this function "
+                                        "returns and stays with the caller: call with smooth = False")
+    log2p1 = _scale_log2(pp.get("signalScale"))
+    import ctypes
+    out = []
+    for s in input:
+        t, n_rows, n_cols, ld = _kept_matrix(s)
+        med = torch.empty(max(n_cols, 1), dtype=torch.float64, device=t.device)
+        mad = torch.empty_like(med)
+        d = _col_desc(t, n_rows, 0, n_cols, ld, log2p1)
+        _lib.check(_lib.lib().rcp_summary_median_mad(ctypes.byref(d), _lib.ptr(med), _lib.ptr(mad),
+                                                     _lib.stream_handle(t.device)))
+        out.append(_band(med[:n_cols].cpu().numpy(), mad[:n_cols].cpu().numpy()))
+    return out

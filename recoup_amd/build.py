@@ -13,7 +13,7 @@ ARCH = os.environ.get("RCP_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
             "-fvisibility=hidden"]
-SOURCES = ["rcp_kernels.hip", "rcp_rle.hip", "rcp_shard.hip", "rcp_summary.hip", "rcp_host.cpp", "rcp_plan.cpp", "rcp_shard.cpp", "rcp_stage.cpp", "rcp_bam.cpp", "rcp_summary.cpp"]
+SOURCES = ["rcp_kernels.hip", "rcp_rle.hip", "rcp_shard.hip", "rcp_summary.hip", "rcp_quantile.hip", "rcp_host.cpp", "rcp_plan.cpp", "rcp_shard.cpp", "rcp_stage.cpp", "rcp_bam.cpp", "rcp_summary.cpp", "rcp_quantile.cpp"]
 DEPS = ["rcp_internal.h", "rcp_plan.h", "rcp_device.h", "rcp_divrn.h", "rcp_rng.h", "rcp_stage.h", "rcp_pack.h", "rcp_splitvector.h", "rcp_rle.h", "rcp_summary.h", os.path.join("..", "..", "include", "recoup_amd.h")]
 
 

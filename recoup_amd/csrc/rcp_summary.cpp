@@ -50,6 +50,10 @@ int64_t at_least_one(int64_t n) { return n > 0 ? n : 1; }
 
 }  // namespace
 
+// the same checks for rcp_quantile.cpp
+int rcpi::summary_check_desc(const rcp_matrix_desc* m) { return check_desc(m); }
+int rcpi::summary_matrix_device(const rcp_matrix_desc* m, int* dev) { return matrix_device(m, dev); }
+
 extern "C" int rcp_summary_cols(const rcp_matrix_desc* m, const int32_t* d_group, int32_t n_groups, double* d_mean,
                                 double* d_sd, int64_t* d_count, void* hip_stream) {
     RCP_TRY

@@ -297,11 +297,6 @@ rcp_rowstats_kernel(const double* __restrict__ mat, int64_t n_rows, int64_t n_co
     if (SD && o_sd) o_sd[row] = n > 1.0 ? sqrt(q / (n - 1.0)) : (double)NAN;
 }
 
-__device__ __forceinline__ uint64_t sort_key(double v) {  // order-preserving 64-bit form of a double
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 __global__ void __launch_bounds__(kBlock)
 rcp_order_keys_kernel(const double* __restrict__ stat, int32_t n_samples, int64_t n_rows, int what, int decreasing,
                       const int32_t* __restrict__ gid, int32_t n_groups, double* __restrict__ d_key,
@@ -325,7 +320,7 @@ rcp_order_keys_kernel(const double* __restrict__ stat, int32_t n_samples, int64_
     }
     // R compares -0.0 and 0.0 equal: one sortable form for both.  Descending is the ascending
     // order of the complemented form, so ties keep row order in both directions.
-    const uint64_t k = sort_key(v == 0.0 ? 0.0 : v);
+    const uint64_t k = rcp_sort_key(v == 0.0 ? 0.0 : v);
     skey[r] = held ? (decreasing ? ~k : k) : 0ull;  // rows no group holds stay in row order
     idx[r] = (int32_t)r;
 }

@@ -12,6 +12,10 @@ generated on the device) this times
   * what a user does without them: ``profile_device.cpu().numpy()`` followed by the NumPy
     reductions (column mean and sd, row sums, a stable argsort);
 
+  * the exact quantiles (quantile_bench below): rcp_summary_quantiles over the whole matrix at the
+    heatmap ladder and per column at 0.5, and rcp_summary_median_mad, each on this input and on one
+    with 70 % zeros, per matrix pass against rcp_summary_cols and against download-and-NumPy;
+
 and prints one JSON line (also written to --out).  It needs a GPU; ``--dry-run`` only checks the
 arguments and prints the byte arithmetic.
 
@@ -64,6 +68,104 @@ def timed(fn, min_time, torch):
     b.record()
     b.synchronize()
     return a.elapsed_time(b) / reps, reps
+
+
+LADDER = [0.95, 0.96, 0.97, 0.98, 0.99, 0.995, 0.999]
+
+
+def host_quantile(x, probs, ranks, np):
+    """The restatement of the type-7 quantile along the last axis of x with np.partition (the
+    elements a sort would put at lo and hi): (1 - h) * x_(lo) + h * x_(hi), rounded separately."""
+    n = x.shape[-1]
+    out = []
+    for p in probs:
+        lo, hi, h = ranks(n, p)
+        part = np.partition(x, sorted({lo - 1, hi - 1}), axis=-1)
+        a, b = part[..., lo - 1], part[..., hi - 1]
+        out.append(np.where(a == b, a, (1.0 - h) * a + h * b))
+    return np.stack(out, axis=-1)
+
+
+def quantile_bench(args, res, buf, torch, np, _lib):
+    """rcp_summary_quantiles (whole matrix, the seven-entry ladder; per column, p = 0.5) and
+    rcp_summary_median_mad on a continuous input and on one with 70 % zeros: milliseconds by device
+    events, the matrix passes each call makes, the time per pass over rcp_summary_cols of the same
+    input in the same run, and the route a user has today (download, then NumPy) with its results
+    compared bit for bit."""
+    n_rows, n_cols, ld = args.rows, args.cols, res["ld"]
+    L = _lib.lib()
+    dev = buf.device
+    st = _lib.stream_handle(dev)
+
+    def ranks(n, p):
+        lo, hi, h = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+        _lib.check(L.rcp_quantile_ranks(n, p, ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(h)))
+        return lo.value, hi.value, h.value
+
+    def passes(n, probs):  # 8 digit passes, one more for x_(hi) when a probability interpolates
+        return 8 + int(any(ranks(n, p)[0] != ranks(n, p)[1] for p in probs))
+
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(args.seed + 1)
+    tied = torch.empty_like(buf)
+    tied.exponential_(0.02, generator=gen)
+    tied.mul_(8.0).floor_().div_(8.0)  # coverage-like repeated values
+    tied[torch.rand(tied.shape, device=dev, generator=gen) < 0.7] = 0.0
+    tied[:, n_rows:] = float("nan")
+    ladder = (ctypes.c_double * len(LADDER))(*LADDER)
+    half = (ctypes.c_double * 1)(0.5)
+    q_mat = torch.empty(len(LADDER), dtype=torch.float64, device=dev)
+    q_col = torch.empty(n_cols, dtype=torch.float64, device=dev)
+    med = torch.empty(n_cols, dtype=torch.float64, device=dev)
+    mad = torch.empty(n_cols, dtype=torch.float64, device=dev)
+    c_mean = torch.empty(n_cols, dtype=torch.float64, device=dev)
+    c_sd = torch.empty_like(c_mean)
+    out = {}
+    for name, full in (("continuous", buf), ("zeros70", tied)):
+        t = full[:, :n_rows]
+        arr = (ctypes.c_void_p * 1)(t.data_ptr())
+        d = _lib.MatrixDesc(n_rows, n_cols, ld, 1, 0, arr)
+        calls = {
+            "cols": (lambda: _lib.check(L.rcp_summary_cols(ctypes.byref(d), None, 1, _lib.ptr(c_mean), _lib.ptr(c_sd),
+                                                           None, st)), 1),
+            "matrix_ladder": (lambda: _lib.check(L.rcp_summary_quantiles(ctypes.byref(d), 0, ladder, len(LADDER),
+                                                                         _lib.ptr(q_mat), st)),
+                              passes(n_rows * n_cols, LADDER)),
+            "column_median": (lambda: _lib.check(L.rcp_summary_quantiles(ctypes.byref(d), 1, half, 1, _lib.ptr(q_col),
+                                                                         st)), passes(n_rows, [0.5])),
+            "median_mad": (lambda: _lib.check(L.rcp_summary_median_mad(ctypes.byref(d), _lib.ptr(med), _lib.ptr(mad),
+                                                                       st)), 2 * passes(n_rows, [0.5])),
+        }
+        r = {}
+        for call, (fn, n_pass) in calls.items():
+            ms, reps = timed(fn, args.min_time, torch)
+            r[call] = {"ms": ms, "reps": reps, "matrix_passes": n_pass, "ms_per_pass": ms / n_pass}
+        for call in list(calls)[1:]:
+            r[call]["pass_over_cols_pass"] = r[call]["ms_per_pass"] / r["cols"]["ms"]
+        # today's route: the whole matrix over PCIe, then NumPy
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        host = t.cpu().numpy()  # (n_cols, n_rows)
+        t1 = time.perf_counter()
+        h_mat = host_quantile(host.reshape(-1), LADDER, ranks, np)
+        t2 = time.perf_counter()
+        h_med = host_quantile(host, [0.5], ranks, np)[:, 0]
+        t3 = time.perf_counter()
+        h_mad = 1.4826 * host_quantile(np.abs(host - h_med[:, None]), [0.5], ranks, np)[:, 0]
+        t4 = time.perf_counter()
+        del host
+        dl = (t1 - t0) * 1e3
+        r["download_numpy"] = {"download_ms": dl, "matrix_ladder_ms": dl + (t2 - t1) * 1e3,
+                               "column_median_ms": dl + (t3 - t2) * 1e3, "median_mad_ms": dl + (t4 - t2) * 1e3}
+        for call in list(calls)[1:]:
+            r[call]["ratio_to_download_numpy"] = r["download_numpy"][call + "_ms"] / r[call]["ms"]
+
+        def same(a, b):
+            return bool(np.array_equal(a.cpu().numpy().view(np.uint64), np.ascontiguousarray(b).view(np.uint64)))
+        r["bits_equal_to_numpy"] = {"matrix_ladder": same(q_mat, h_mat), "column_median": same(q_col, h_med),
+                                    "median": same(med, h_med), "mad": same(mad, h_mad)}
+        out[name] = r
+    return out
 
 
 def main(argv=None):
@@ -158,6 +260,8 @@ def main(argv=None):
     res["max_rel_diff_mean"] = float(np.max(np.abs(curve[0]["profile"] - h_mean) / np.abs(h_mean)))
     res["max_rel_diff_sd"] = float(np.max(np.abs((curve[0]["upper"] - curve[0]["profile"]) - h_sd) / h_sd))
     res["order_rows_differing"] = int((order["ix"] != h_ix).sum())  # (sums round differently: near-ties may swap)
+    del host
+    res["quantiles"] = quantile_bench(args, res, buf, torch, np, _lib)
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line)
